@@ -5,7 +5,7 @@ A "step" is one pass of the hot path — mj_step1 + controller + [mj_inverse] + 
 src/mj_main.cpp:82-112) — over one batch of environments per GPU, one launch per step and cohort (the drop-in keeps the
 reference's per-step host hand-off to ros_control).  Inputs are resident in HBM when the timed region starts.
 
-    python bench.py --gpus N --steps K --warmup W [--config s24|c2|c3|c4|c5]
+    python bench.py --gpus N --steps K --warmup W [--config s24|c2|c3|c4|c5] [--dump-outputs DIR] [--full]
 
 Every config first runs its FIXED, untimed settle phase (S24 400 steps, C2 200, ...) — independent
 of --warmup — so that the timed window always steps the scene the metric names; then W untimed warm-up steps, then EXACTLY K
@@ -13,6 +13,13 @@ timed steps bracketed by barrier + synchronize.  N > 1: launched by torch.distri
 are sharded (rank r owns envs [r*n, (r+1)*n)), no data-path collective; the only collective is the RCCL all-gather of the
 published state slice at 60 Hz of simulated time, packed (mjh_export_state_device) at that rate at every N
 so that per-GPU work does not depend on N.  Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline needs: set-up, settle, warm-up, the K timed steps, the line.  --full adds what takes runs
+of its own: the second timed window (the other mj_inverse variant), the CPU baseline, and for S24 at N = 1 the literal reference
+loop and the other BASELINE configs, each in a process of its own (--no-second-window / --no-cpu-baseline / --no-extra-configs
+drop one of them again).  --dump-outputs DIR writes the state the timed path leaves after its last step (what mjh_get_state and
+mjh_get_stats hand a caller), per environment, as DIR/<name>.npy in float64: the inputs are seeded, so two builds run with the
+same arguments can be compared array for array.
 """
 import argparse
 import json
@@ -476,6 +483,12 @@ def run_group_host(args):
     t0 = time.perf_counter(); run(args.steps); t_issued = time.perf_counter() - t0; g.synchronize(); elapsed = time.perf_counter() - t0
     kernel_ms, n_timed = g.engines[0].get_launch_timing(); g.engines[0].set_launch_timing(False)
     issue_timed = dict(issue)
+    if args.dump_outputs:
+        states = [e.get_state() for e in g.engines]
+        save_outputs(args.dump_outputs, {"time": np.concatenate([x[0] for x in states]), "qpos": np.concatenate([x[1] for x in states]),
+                                         "qvel": np.concatenate([x[2] for x in states]), "qacc_warmstart": np.concatenate([x[3] for x in states]),
+                                         "stats": np.concatenate([e.get_stats().astype(np.float64) for e in g.engines]),
+                                         "env_ids": np.concatenate([np.arange(lo, lo + n, dtype=np.float64) for lo, n in g.ranges])})
     # the exchange's own duration: a second, short window (reading the event pair of the previous publish makes the host wait for it —
     # kept out of the timed window, whose host time is the issue time reported below)
     g.set_publish_timing(True); run(min(args.steps, 20 * publish_every)); g.synchronize()
@@ -615,6 +628,35 @@ def literal_loop_line(w, steps):
             "fused_step_with_per_step_read_write": {"value": w.nenv * steps / dt2, "ms_per_step": dt2 / steps * 1e3}}
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(w, out_dir, rank=0, world=1):
+    """The state the timed path leaves after its last step, per environment, as <out_dir>/<name>.npy (float64; the device's fp32
+    values convert exactly): time, qpos, qvel, qacc_warmstart (mjh_get_state) and stats = ncon, nefc, solver sweeps, flags of the
+    environment's wavefront (mjh_get_stats).  env_ids holds the global ids of the rows written: every environment, or a fixed,
+    seeded sample of them where the whole set would exceed 64 MB.  N > 1: one set per rank, the names suffixed _rank<r>."""
+    n = w.nenv
+    q, v, ws, _ = w.env_state(n)
+    t = w.eng.get_state(0, w.rows)[0]
+    st = w.eng.get_stats(0, w.rows)
+    save_outputs(out_dir, {"time": np.repeat(t, w.pack)[:n], "qpos": q, "qvel": v, "qacc_warmstart": ws,
+                           "stats": np.repeat(st.astype(np.float64), w.pack, axis=0)[:n],
+                           "env_ids": np.arange(w.env_offset, w.env_offset + n, dtype=np.float64)}, f"_rank{rank}" if world > 1 else "")
+
+
+def save_outputs(out_dir, arrs, sfx=""):
+    """arrays of one row per environment -> <out_dir>/<name><sfx>.npy in float64, a seeded sample of the rows above the 64 MB budget"""
+    n = len(arrs["env_ids"])
+    total = sum(a.size * 8 for a in arrs.values())
+    if total > DUMP_BUDGET_BYTES:
+        keep = np.sort(np.random.default_rng(0x0D0).choice(n, max(1, n * DUMP_BUDGET_BYTES // total), replace=False))
+        arrs = {k: a[keep] for k, a in arrs.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, f"{k}{sfx}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -640,9 +682,12 @@ def main():
                     help="N > 1: `ranks` = one process per GPU over torch.distributed (what the driver launches; a plain invocation re-executes itself "
                          "under torch.distributed.run), `group` = ONE process driving every GPU through mjh_group_* (the C host API, RCCL all-gather)")
     ap.add_argument("--group-devices", default="", help="--host group: comma-separated device list (default 0..N-1; the same device twice is a one-GPU self-test on peer copies)")
-    ap.add_argument("--no-extra-configs", action="store_true", help="S24 at N = 1 appends short lines of the other BASELINE configs (c2..c5) and the literal loop; skip them")
+    ap.add_argument("--no-extra-configs", action="store_true", help="--full, S24 at N = 1 appends short lines of the other BASELINE configs (c2..c5) and the literal loop; skip them")
     ap.add_argument("--extra-steps", type=int, default=0, help="timed steps of each appended config line (0: the config's own D3 window, EXTRA_WINDOWS — what the driver's line carries)")
     ap.add_argument("--rank-probe", action="store_true", help=argparse.SUPPRESS)     # tests: every rank prints its rank / world size and exits
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own: second timed window, CPU baseline, "
+                                                           "literal loop and the other configs (S24 at N = 1); off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write the state after the last timed step as DIR/<name>.npy (float64)")
     ap.add_argument("--cpu-envs", type=int, default=1024)
     ap.add_argument("--cpu-seconds", type=float, default=16.0, help="time budget of the CPU baseline sample")
     args = ap.parse_args()
@@ -663,7 +708,7 @@ def main():
         return
 
     # the other configs first, each in a process of its own, while this process has not created a stream yet (child_config_line)
-    with_extras = rank == 0 and world == 1 and args.config == "s24" and not args.no_extra_configs and not args.force_dist
+    with_extras = args.full and rank == 0 and world == 1 and args.config == "s24" and not args.no_extra_configs and not args.force_dist
     extras_last = os.environ.get("BENCH_EXTRAS_LAST", "0") == "1"
     extras = extra_config_lines(args) if (with_extras and not extras_last) else None
 
@@ -759,11 +804,13 @@ def main():
     spl = int(eng.steps_per_launch) if args.no_gather else min(int(eng.steps_per_launch), publish_every)
     n_launches = -(-args.steps // spl) * G
     achieved = bytes_step * envs_per_launch * spl / (kernel_ms * 1e-3) / 1e9
+    if args.dump_outputs:
+        dump_outputs(w, args.dump_outputs, rank, world)
 
-    # 4. the other mj_inverse variant, same K steps (the reference always pays mj_inverse,
+    # 4. (--full) the other mj_inverse variant, same K steps (the reference always pays mj_inverse,
     # mj_hw_interface.cpp:61 — report both)
     other = None
-    if not args.no_second_window:
+    if args.full and not args.no_second_window:
         e2, k2, n2 = timed(args.steps, not main_inverse)
         other = {"value": total_envs * args.steps / e2, "ms_per_step": e2 / args.steps * 1e3, "kernel_ms": k2}
 
@@ -850,7 +897,7 @@ def main():
             out["literal_loop"] = literal_loop_line(w, max(50, min(args.steps, 200)))
         except Exception as ex:   # an extra must never cost the headline
             out["literal_loop"] = {"error": repr(ex)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:   # the CPU baseline is timed at N = 1 only
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:   # the CPU baseline is timed at N = 1 only
         out["cpu_baseline"] = cpu_baseline(w, args.cpu_envs, args.cpu_seconds, main_inverse)
     if use_dist:
         dist.barrier()

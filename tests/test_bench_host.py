@@ -108,3 +108,18 @@ def test_timed_team_steps_every_env_exactly_as_the_plain_loop():
     for x, y in zip(a, b):
         np.testing.assert_array_equal(x.f("qpos"), y.f("qpos")); np.testing.assert_array_equal(x.f("qvel"), y.f("qvel"))
     L.orc_set_threads(1)
+
+
+def test_dumped_outputs_are_float64_and_sampled_the_same_way_above_the_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every row below 64 MB; above it the same seeded sample of rows in every array, whatever ran"""
+    n = 1000
+    arrs = {"qpos": np.arange(n * 7, dtype=np.float64).reshape(n, 7), "stats": np.ones((n, 4), np.int32), "env_ids": np.arange(n, dtype=np.float64)}
+    bench.save_outputs(str(tmp_path / "all"), arrs)
+    z = {k: np.load(tmp_path / "all" / f"{k}.npy") for k in arrs}
+    assert all(a.dtype == np.float64 for a in z.values()) and np.array_equal(z["qpos"], arrs["qpos"]) and len(z["env_ids"]) == n
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 8 * 12 * 100)          # room for 100 rows of 12 values
+    for d in ("s1", "s2"):
+        bench.save_outputs(str(tmp_path / d), arrs, "_rank1")
+    a, b = (np.load(tmp_path / d / "env_ids_rank1.npy") for d in ("s1", "s2"))
+    q = np.load(tmp_path / "s1" / "qpos_rank1.npy")
+    assert len(a) == 100 and np.array_equal(a, b) and np.all(np.diff(a) > 0) and np.array_equal(q, arrs["qpos"][a.astype(int)])

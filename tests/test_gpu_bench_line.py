@@ -1,11 +1,13 @@
-"""The driver's contract, end to end on the GPU box: `python bench.py` prints ONE JSON line whose metric is BASELINE.json's, with the
-roofline and cpu_baseline objects, the literal loop and the other configs riding along; the one-process group host runs without a
-launcher.  (Short windows: this checks the shape and sanity of the line, not the numbers.)"""
+"""The driver's contract, end to end on the GPU box: `python bench.py` prints ONE JSON line whose metric is BASELINE.json's; with
+--full the cpu_baseline object, the literal loop and the other configs ride along; --dump-outputs writes the state of the last timed
+step; the one-process group host runs without a launcher.  (Short windows: this checks the shape and sanity of the line, not the
+numbers.)"""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -25,7 +27,7 @@ def _run(args, timeout=900):
 
 def test_driver_line_has_everything_the_contract_names():
     base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
-    r = _run(["--steps", "12", "--warmup", "3", "--cpu-seconds", "4", "--extra-steps", "6"])
+    r = _run(["--full", "--steps", "12", "--warmup", "3", "--cpu-seconds", "4", "--extra-steps", "6"])
     assert r["metric"] == base["metric"] and r["unit"] == "env-steps/s" and r["n_gpus"] == 1 and r["steps"] == 12 and r["warmup"] == 3
     assert r["higher_is_better"] is True and r["scaling"] == "weak" and r["vs_baseline"] is None and r["dtype"] == "f32" and r["data"] == "synthetic"
     assert r["value"] > 1e6 and abs(r["value"] - 4096 * 12 / (r["ms_per_step"] * 12e-3)) < 1e-3 * r["value"]
@@ -61,6 +63,26 @@ def test_driver_line_has_everything_the_contract_names():
     assert c30["overflow_envs"] == 0 and 24 <= c30["mean_ncon"] <= 40 and sum(c30["ncon_histogram"].values()) == 4096 and sum(c30["nefc_histogram"].values()) == 4096
     assert sum(r["configs"]["c2"]["ncon_histogram"].values()) == 4096
     assert r["configs"]["s24d"]["mean_ncon"] >= 20 and r["configs"]["c2"]["mean_ncon"] >= 100 and r["configs"]["c4"]["mean_nefc"] >= 50
+
+
+def test_plain_line_is_the_headline_and_dumps_the_last_timed_step(tmp_path):
+    """without --full: the headline and its own window only (no second window, CPU baseline, literal loop or other configs);
+    --dump-outputs: the per-env state after the last of the K timed steps, float64, every env"""
+    base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
+    r = _run(["--gpus", "1", "--steps", "12", "--warmup", "3", "--dump-outputs", str(tmp_path)])
+    assert r["metric"] == base["metric"] and r["unit"] == "env-steps/s" and r["higher_is_better"] is True and r["dtype"] == "f32"
+    assert r["steps"] == 12 and r["warmup"] == 3 and r["value"] > 1e6 and abs(r["value"] - 4096 * 12 / (r["ms_per_step"] * 12e-3)) < 1e-3 * r["value"]
+    assert r["roofline"]["kernel_ms"] > 0 and "unsettled" not in r
+    for k in ("cpu_baseline", "literal_loop", "configs", "second_window", "value_with_inverse", "value_30_contact"):
+        assert k not in r, k
+    z = {k: np.load(os.path.join(tmp_path, f"{k}.npy")) for k in ("time", "qpos", "qvel", "qacc_warmstart", "stats", "env_ids")}
+    assert all(a.dtype == np.float64 and len(a) == 4096 and np.isfinite(a).all() for a in z.values())
+    assert z["qpos"].shape == (4096, 28) and z["qvel"].shape == z["qacc_warmstart"].shape == (4096, 24) and z["stats"].shape == (4096, 4)
+    assert np.array_equal(z["env_ids"], np.arange(4096))
+    # settle + warm-up + timed steps of simulated time, every env
+    import mujoco_sim_amd as ms
+    dt = ms.scene("s24").opt.timestep
+    assert np.allclose(z["time"], (400 + 3 + 12) * dt, rtol=1e-5, atol=0) and z["stats"][:, 0].mean() >= 8
 
 
 def test_group_host_runs_in_one_process_without_a_launcher():

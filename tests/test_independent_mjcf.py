@@ -4,8 +4,8 @@ loader defect is invisible to the GPU parity tests).  For pr2, tiago, hsrb4s, ri
 models C4 and the robot fixtures are compiled from) every kinematic and inertial table the file states explicitly is rebuilt here — body tree in
 document order, frames, explicit <inertial> (mass, centre, inertia tensor), joints (type, axis, anchor, range under autolimits, damping,
 armature, friction loss), joint equalities with their polycoef, primitive geoms — and compared (i) with the model the product's loader compiles
-from the same file and (ii) with the committed fixture tables under tests/golden (what the GPU box steps).  CPU container only: the reference
-tree does not exist on the GPU box."""
+from the same file and (ii) with the committed fixture tables under tests/golden (what the GPU box steps).  The robot files come from
+tests/golden/reference_models.npz (tests/refmodels.py)."""
 import os
 import xml.etree.ElementTree as ET
 
@@ -15,15 +15,14 @@ import pytest
 import mujoco_sim_amd as ms
 from indep_dyn import quat2mat
 from mujoco_sim_amd.tables import load_model_tables
+from refmodels import model_dir
 
-REF = "/root/reference/model/test"
+REF = os.path.join(model_dir(), "test")
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 ROBOTS = {"pr2": "pr2/pr2.xml", "tiago": "tiago/tiago.xml", "hsrb4s": "hsrb4s/hsrb4s.xml", "ridgeback_panda": "ridgeback_panda/ridgeback_panda.xml",
           "armar6": "armar/armar6.xml"}
 GEOM = {"plane": 0, "sphere": 2, "capsule": 3, "ellipsoid": 4, "cylinder": 5, "box": 6, "mesh": 7}
 JNT = {"free": 0, "ball": 1, "slide": 2, "hinge": 3}
-
-pytestmark = pytest.mark.skipif(not os.path.exists(os.path.join(REF, "pr2", "pr2.xml")), reason="reference tree absent (GPU box)")
 
 
 def _f(el, key, default):

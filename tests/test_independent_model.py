@@ -20,6 +20,7 @@ from indep_dyn import quat2mat
 from indep_model import compile_scene, scene_arm7, scene_pendulum, scene_s24
 from mujoco_sim_amd import capi
 from mujoco_sim_amd.engine import EP
+from refmodels import model_dir
 
 SCENES = {"s24": (lambda: ms.scene("s24"), lambda: scene_s24()),
           "s24d": (lambda: ms.scene("s24pen", 0.175, 96), lambda: scene_s24(0.175)),
@@ -61,11 +62,9 @@ def test_product_compiler_tables_equal_the_independent_construction(name):
 
 
 def test_the_scene_descriptions_are_the_reference_files_numbers():
-    """the pendulum world and the Panda chain as the reference's own files state them (read here with the standard library's XML parser:
-    /root/reference exists on the build box only — the numbers in tests/indep_model.py are the data, this test is what checks them)"""
-    ref = "/root/reference/model/test"
-    if not os.path.exists(os.path.join(ref, "pendulum.xml")):
-        pytest.skip("reference tree absent (GPU box)")
+    """the pendulum world and the Panda chain as the reference's own files state them (read here with the standard library's XML parser
+    from tests/golden/reference_models.npz — the numbers in tests/indep_model.py are the data, this test is what checks them)"""
+    ref = os.path.join(model_dir(), "test")
     root = ET.parse(os.path.join(ref, "pendulum.xml")).getroot()
     opt = root.find("option")
     sc = scene_pendulum()

@@ -8,6 +8,7 @@ import pytest
 import mujoco_sim_amd as ms
 import orc
 from helpers import D, set_opt
+from refmodels import model_dir
 
 ARM = """<?xml version="1.0"?>
 <mujoco model="two_link">
@@ -96,10 +97,9 @@ def test_loader_rejects_malformed_input(lib):
     assert not lib.mjh_load_mjcf_file(b"/no/such/file.xml")
 
 
-REF_PENDULUM = "/root/reference/model/test/pendulum.xml"
+REF_PENDULUM = os.path.join(model_dir(), "test", "pendulum.xml")
 
 
-@pytest.mark.skipif(not os.path.exists(REF_PENDULUM), reason="reference tree only exists in the CPU container")
 def test_reference_pendulum_xml_equals_the_restated_scene(lib):
     """C1: the programmatic scene (csrc/scenes.cpp) restates model/test/pendulum.xml exactly"""
     a = ms.load_mjcf(path=REF_PENDULUM)

@@ -22,9 +22,10 @@ import mujoco_sim_amd as ms
 import orc
 from helpers import D, oracle_s24, set_opt
 from mujoco_sim_amd.tables import load_model_tables
+from refmodels import model_dir
 
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-REF = "/root/reference"
+MODEL = model_dir()          # the reference's model/ tree (tests/golden/reference_models.npz)
 
 
 # ----------------------------------------------------------------------------- 1. visiting order
@@ -358,7 +359,6 @@ def _read_binary_stl(path):
     return raw[:, 12:48].copy().view("<f4").reshape(n * 3, 3).astype(np.float64)
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "model/test/pr2")), reason="the reference's mesh assets are only present in the build container")
 def test_decimated_hulls_support_the_full_pr2_meshes(lib):
     """The builder keeps only the vertices of a mesh that are extreme along 1526 directions.  For every STL asset of the
     reference's PR2 (pr2.xml:5-22) the support function of the kept set equals that of the FULL vertex set along those
@@ -366,7 +366,7 @@ def test_decimated_hulls_support_the_full_pr2_meshes(lib):
     vertices; an inner approximation, never outside)."""
     import glob
     import xml.etree.ElementTree as ET
-    root = ET.parse(os.path.join(REF, "model/test/pr2/pr2.xml")).getroot()
+    root = ET.parse(os.path.join(MODEL, "test/pr2/pr2.xml")).getroot()
     meshdir = root.find("compiler").get("meshdir") or ""
     files = sorted({(e.get("file"), e.get("scale") or "1 1 1") for e in root.find("asset").findall("mesh")})
     assert len(files) >= 10
@@ -374,9 +374,9 @@ def test_decimated_hulls_support_the_full_pr2_meshes(lib):
     dirs = rng.normal(size=(4000, 3)); dirs /= np.linalg.norm(dirs, axis=1, keepdims=True)
     worst = 0.0
     for fn, scale in files:
-        path = os.path.normpath(os.path.join(REF, "model/test/pr2", meshdir, fn))
+        path = os.path.normpath(os.path.join(MODEL, "test/pr2", meshdir, fn))
         if not os.path.exists(path):
-            cand = glob.glob(os.path.join(REF, "model", "**", os.path.basename(fn)), recursive=True)
+            cand = glob.glob(os.path.join(MODEL, "**", os.path.basename(fn)), recursive=True)
             assert cand, fn
             path = cand[0]
         sc = np.array([float(x) for x in scale.split()])

@@ -10,6 +10,7 @@ import pytest
 import orc
 from conftest import ROOT
 from helpers import load_model_tables
+from refmodels import model_dir
 
 ROBOTS = ["pr2", "tiago", "hsrb4s", "ridgeback_panda", "pr2_world", "hsrb4s_world", "pr2_mesh", "pr2_world_mesh", "c5_pendulum_bowl_mesh",
           "c4_pr2_world_objects_mesh", "tiago_mesh", "hsrb4s_mesh", "armar6_mesh", "ridgeback_panda_mesh"]
@@ -26,7 +27,7 @@ FILES = {"pr2": "pr2/pr2.xml", "tiago": "tiago/tiago.xml", "hsrb4s": "hsrb4s/hsr
          # (loaded with mjh_load_set_parent_child_exclude(2): the wrapper's disable_parent_child_collision_level, mujoco_compile.cpp:250-290)
          "ridgeback_panda_mesh": "ridgeback_panda/ridgeback_panda.xml"}
 PC_EXCLUDE = {"ridgeback_panda_mesh": 2}
-REF = "/root/reference/model/test"
+REF = os.path.join(model_dir(), "test")
 
 
 def robot_command(m, k):
@@ -67,7 +68,6 @@ def test_oracle_reproduces_robot_golden(lib, name):
     assert np.isfinite(d.f("qpos")).all()
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box)")
 @pytest.mark.parametrize("name", ROBOTS)
 def test_loader_still_produces_the_fixture_tables(lib, name):
     if FILES[name] is None:

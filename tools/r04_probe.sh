@@ -24,7 +24,7 @@ PY
 for c in 2 3 4 6; do run c2_c$c c2 A=1 -- --cohorts $c; done
 run c2_w2 c2 MJH_SOLVE_WAVES=2 -- --cohorts 3
 for c in 2 3 4 6; do run c4_c$c c4 A=1 -- --cohorts $c; done
-timeout 600 python bench.py > $OUT/bench_driver.json 2> $OUT/bench_driver.err; echo "bench rc=$?"
+timeout 600 python bench.py --full > $OUT/bench_driver.json 2> $OUT/bench_driver.err; echo "bench rc=$?"
 python - <<PY
 import json
 r = json.loads(open("$OUT/bench_driver.json").read().strip().splitlines()[-1])

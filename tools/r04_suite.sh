@@ -10,7 +10,7 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   timeout 2400 python -m pytest tests -m gpu -x -q > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?" | tee -a $OUT/pytest_gpu.log
   tail -5 $OUT/pytest_gpu.log
 fi
-timeout 600 python bench.py > $OUT/bench_driver.json 2> $OUT/bench_driver.err; echo "bench rc=$?"
+timeout 600 python bench.py --full > $OUT/bench_driver.json 2> $OUT/bench_driver.err; echo "bench rc=$?"
 python - <<PY
 import json
 r = json.loads(open("$OUT/bench_driver.json").read().strip().splitlines()[-1])

@@ -3,7 +3,7 @@
 set -u
 O=gpurun_out/r06a; mkdir -p $O
 ( time python -m pytest tests/test_gpu_round6.py tests/test_gpu_bench_line.py "tests/test_gpu_round5.py::test_launch_chain_as_a_captured_graph_equals_the_separate_launches" -x -q -m gpu -s ) > $O/pytest_new.log 2>&1; echo "pytest rc=$?"; grep -E "WINDOW-CLAMP|passed|failed|Error|error" $O/pytest_new.log | head -20
-( time python bench.py --gpus 1 --steps 20 --warmup 5 ) > $O/bench_driver.json 2> $O/bench_driver.err; echo "bench rc=$?"; tail -3 $O/bench_driver.err
+( time python bench.py --full --gpus 1 --steps 20 --warmup 5 ) > $O/bench_driver.json 2> $O/bench_driver.err; echo "bench rc=$?"; tail -3 $O/bench_driver.err
 python - <<'PY'
 import json
 d=json.loads(open("gpurun_out/r06a/bench_driver.json").read().strip().splitlines()[-1])

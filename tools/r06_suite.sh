@@ -12,7 +12,7 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   tail -6 $OUT/pytest_gpu.log
   python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $OUT/smoke.log
 fi
-( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 ) > $OUT/bench_driver.json 2> $OUT/bench_driver.err; echo "bench rc=$?"; tail -4 $OUT/bench_driver.err
+( time timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 ) > $OUT/bench_driver.json 2> $OUT/bench_driver.err; echo "bench rc=$?"; tail -4 $OUT/bench_driver.err
 python - <<PY
 import json
 r = json.loads(open("$OUT/bench_driver.json").read().strip().splitlines()[-1])
