@@ -44,6 +44,9 @@ enum mjh_geom {
   MJH_GEOM_ELLIPSOID = 4, MJH_GEOM_CYLINDER = 5, MJH_GEOM_BOX = 6, MJH_GEOM_MESH = 7
 };
 
+/* contacts one (hfield, geom) pair can produce: the first ones in prism order are kept (MuJoCo's mjMAXCONPAIR) */
+#define MJH_HFIELD_MAXCON 50
+
 enum mjh_eq { MJH_EQ_CONNECT = 0, MJH_EQ_WELD = 1, MJH_EQ_JOINT = 2 };
 /* sensor types: values follow mjtSensor; the reference publishes exactly these two (MjSim::init_sensors, mj_sim.cpp:973-1014) */
 enum mjh_sensor { MJH_SENS_FORCE = 4, MJH_SENS_TORQUE = 5 };
@@ -150,6 +153,15 @@ typedef struct mjh_model {
    *   weld:    [0..2] anchor in body2's frame, [3..5] the same point in body1's frame at qpos0,
    *            [6..9] relative orientation quat(body2)^-1 * quat(body1) at qpos0, [10] torquescale */
   int* body_mocapid;
+  /* ---- appended for height fields (older fields keep their offsets) ----
+   * <asset><hfield>: an nrow x ncol elevation grid, row-major, normalised to [0, 1] at compile time.  Grid point (r, c) lies at
+   * x = -size[0] + 2 size[0] c / (ncol - 1), y = -size[1] + 2 size[1] r / (nrow - 1), z = data size[2] in the geom's frame; the
+   * terrain reaches down to z = -size[3].  geom_dataid of an hfield geom holds its hfield id. */
+  int nhfield, nhfielddata;
+  int *hfield_nrow, *hfield_ncol, *hfield_adr;  /* [nhfield] */
+  double* hfield_size;                          /* [4*nhfield]: radius_x, radius_y, elevation_z, base_z */
+  double* hfield_data;                          /* [nhfielddata] */
+  char** hfield_names;
 } mjh_model;
 
 /* ------------------------------------------------- model builder (host) */
@@ -187,6 +199,15 @@ int mjh_builder_add_mesh_stl(mjh_builder*, const char* path, const double scale[
 /* mesh geom: pos/quat place the MESH FILE's frame in the body, as <geom type="mesh" pos quat> does */
 int mjh_builder_add_mesh_geom(mjh_builder*, const char* name, int body, int mesh, const double pos[3], const double quat[4],
                               const double friction[3], int condim, int contype, int conaffinity, double density);
+/* height field asset (<asset><hfield nrow ncol size elevation>): elevation row-major [nrow*ncol] (NULL: zeros), normalised to
+ * [0, 1] at compile time (minus the minimum, divided by max - min when that is non-zero); size = radius_x, radius_y,
+ * elevation_z, base_z, each > 0; nrow, ncol >= 2.  Returns the hfield id (>= 0) or a negative code. */
+int mjh_builder_add_hfield(mjh_builder*, const char* name, int nrow, int ncol, const double size[4], const double* elevation);
+/* hfield geom: on a static body only (body_weldid 0; otherwise MJH_ERR_UNSUPPORTED), massless.  It collides with spheres,
+ * capsules, ellipsoids, cylinders, boxes and meshes as triangular prisms, one contact per prism, at most 50 per pair.
+ * (mjh_builder_add_geom with type MJH_GEOM_HFIELD keeps a geom without an asset: it has no pairs.) */
+int mjh_builder_add_hfield_geom(mjh_builder*, const char* name, int body, int hfield, const double pos[3], const double quat[4],
+                                const double friction[3], int condim, int contype, int conaffinity);
 int mjh_builder_add_exclude(mjh_builder*, int body1, int body2);
 int mjh_builder_add_eq_joint(mjh_builder*, int joint1, int joint2, const double polycoef[5]);
 /* <equality><connect body1 body2 anchor> / <weld body1 body2 anchor torquescale> (body2 = 0: the world).  connect: `anchor`

@@ -19,6 +19,7 @@ SOURCES = {
     "engine.hip": KERNEL_HEADERS + [API],
     "window.hip": WINDOW_HEADERS + [API],
     "dense.hip": DENSE_HEADERS + [API],
+    "hfield.hip": KERNEL_HEADERS + [API],
     "group.hip": ["host_pool.h", API],
     "model_builder.cpp": ["hmath.h", API],
     "scenes.cpp": ["hmath.h", API],
@@ -50,7 +51,7 @@ def build(force=False, verbose=False):
     """hipcc --offload-arch=gfx950: cross-compiles without a GPU."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     os.makedirs(OBJ, exist_ok=True)
-    objs, digests = [], []
+    objs, digests, stale = [], [], []
     for src, deps in SOURCES.items():
         sp = os.path.join(CSRC, src)
         if not os.path.exists(sp):
@@ -61,13 +62,21 @@ def build(force=False, verbose=False):
         stamp = op + ".sha256"
         have = open(stamp).read().strip() if os.path.exists(stamp) else ""
         if force or not os.path.exists(op) or have != dg:
-            cmd = [hipcc] + sflags + ["-c", sp, "-o", op]
-            if verbose:
-                print(" ".join(cmd), file=sys.stderr)
-            subprocess.check_call(cmd)
-            with open(stamp, "w") as f:
-                f.write(dg)
+            stale.append(([hipcc] + sflags + ["-c", sp, "-o", op], stamp, dg))
         objs.append(op); digests.append(dg)
+    # the stale units compile side by side (engine.hip and hfield.hip each take minutes); a few at a time
+    from concurrent.futures import ThreadPoolExecutor
+
+    def _compile(job):
+        cmd, stamp, dg = job
+        if verbose:
+            print(" ".join(cmd), file=sys.stderr)
+        subprocess.check_call(cmd)
+        with open(stamp, "w") as f:
+            f.write(dg)
+    with ThreadPoolExecutor(max_workers=max(1, min(4, len(stale)))) as pool:
+        for r in [pool.submit(_compile, j) for j in stale]:
+            r.result()
     link_dg = _digest([], " ".join(digests))
     link_stamp = os.path.join(OBJ, "libmjhip.sha256")
     have = open(link_stamp).read().strip() if os.path.exists(link_stamp) else ""

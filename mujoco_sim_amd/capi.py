@@ -70,6 +70,12 @@ _ARRAYS2 = [
     ("sensor_type", "i", "nsensor"), ("sensor_objid", "i", "nsensor"), ("sensor_adr", "i", "nsensor"),
 ]
 _ARRAYS3 = [("body_mocapid", "i", "nbody")]
+# appended for height fields (behind body_mocapid)
+_INT_SIZES4 = ["nhfield", "nhfielddata"]
+_ARRAYS4 = [
+    ("hfield_nrow", "i", "nhfield"), ("hfield_ncol", "i", "nhfield"), ("hfield_adr", "i", "nhfield"),
+    ("hfield_size", "d", "4*nhfield"), ("hfield_data", "d", "nhfielddata"),
+]
 
 
 class Model(C.Structure):
@@ -83,15 +89,18 @@ class Model(C.Structure):
         + [(n, c_int_p if t == "i" else c_double_p) for n, t, _ in _ARRAYS2]
         + [("site_names", C.POINTER(C.c_char_p)), ("sensor_names", C.POINTER(C.c_char_p))]
         + [(n, c_int_p if t == "i" else c_double_p) for n, t, _ in _ARRAYS3]
+        + [(n, C.c_int) for n in _INT_SIZES4]
+        + [(n, c_int_p if t == "i" else c_double_p) for n, t, _ in _ARRAYS4]
+        + [("hfield_names", C.POINTER(C.c_char_p))]
     )
 
     def array(self, name):
         """numpy copy of a model array."""
         import numpy as np
 
-        for n, t, expr in _ARRAYS + _ARRAYS2 + _ARRAYS3:
+        for n, t, expr in _ARRAYS + _ARRAYS2 + _ARRAYS3 + _ARRAYS4:
             if n == name:
-                ln = eval(expr, {}, {k: getattr(self, k) for k in _INT_SIZES + _INT_SIZES2})
+                ln = eval(expr, {}, {k: getattr(self, k) for k in _INT_SIZES + _INT_SIZES2 + _INT_SIZES4})
                 ptr = getattr(self, n)
                 if ln == 0 or not ptr:
                     return np.zeros(0, dtype=np.int32 if t == "i" else np.float64)
@@ -124,6 +133,9 @@ SYMBOLS = [
                                       c_double_p, C.c_int, C.c_int, C.c_int, C.c_double]),
     ("mjh_builder_add_mesh", C.c_int, [_vp, c_double_p, C.c_int, c_int_p, C.c_int, c_double_p]),
     ("mjh_builder_add_mesh_stl", C.c_int, [_vp, C.c_char_p, c_double_p]),
+    ("mjh_builder_add_hfield", C.c_int, [_vp, C.c_char_p, C.c_int, C.c_int, c_double_p, c_double_p]),
+    ("mjh_builder_add_hfield_geom", C.c_int, [_vp, C.c_char_p, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p,
+                                             C.c_int, C.c_int, C.c_int]),
     ("mjh_builder_add_mesh_geom", C.c_int, [_vp, C.c_char_p, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p,
                                            C.c_int, C.c_int, C.c_int, C.c_double]),
     ("mjh_builder_add_exclude", C.c_int, [_vp, C.c_int, C.c_int]),

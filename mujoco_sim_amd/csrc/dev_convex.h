@@ -120,14 +120,44 @@ DEV void mesh_support_wave(const bool want, const float* vert, const int nvert, 
     }
   }
 }
-// support points of both geoms of every active lane along +-dir; mesh scans are served by the wave (converged call)
-DEV void mpr_support_wave(const CvxGeom& g1, const CvxGeom& g2, const float* dir, MprPt& p, const bool act, const int lane) {
+// one triangular prism of a height field (the HF kernel instances): its three corners in the hfield's frame relative to the
+// prism's centre (the mean of its six vertices), their top heights and the common bottom
+struct HfPrism { float x[3], y[3], top[3], bot; };
+// support point of a prism along dl: per corner the top vertex when dl_z >= 0, the bottom one otherwise, then the corner with
+// the largest projection (ties: the first corner — a scan over the vertices [tops..., bottoms...] keeps the same one)
+DEV void prism_support_local(const HfPrism& h, const float* dl, float* pl) {
+  const bool up = dl[2] >= 0;
+  float bd = -3.0e38f;
+  pl[0] = h.x[0]; pl[1] = h.y[0]; pl[2] = up ? h.top[0] : h.bot;
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    const float z = up ? h.top[i] : h.bot, d = h.x[i]*dl[0] + h.y[i]*dl[1] + z*dl[2];
+    const bool take = d > bd;
+    bd = take ? d : bd; pl[0] = take ? h.x[i] : pl[0]; pl[1] = take ? h.y[i] : pl[1]; pl[2] = take ? z : pl[2];
+  }
+}
+// farthest vertex of one hull along dl, scanned by the lane itself (ties: the lowest index, as the wave-served scan keeps it)
+DEV void mesh_support_lane(const float* vert, const int nvert, const float* dl, float* pl) {
+  float bd = -3.0e38f;
+  for (int i = 0; i < nvert; i++) {
+    const float x = vert[3*i], y = vert[3*i+1], z = vert[3*i+2], dp = x*dl[0] + y*dl[1] + z*dl[2];
+    if (dp > bd) { bd = dp; pl[0] = x; pl[1] = y; pl[2] = z; }
+  }
+}
+// support points of both geoms of every active lane along +-dir; mesh scans are served by the wave (converged call).
+// PRISM: geom1 is the height-field prism *h (its frame: g1.pos / g1.mat)
+template <bool PRISM = false>
+DEV void mpr_support_wave(const CvxGeom& g1, const CvxGeom& g2, const float* dir, MprPt& p, const bool act, const int lane, const HfPrism* h = nullptr) {
   const float nd[3] = {-dir[0], -dir[1], -dir[2]};
   float dl1[3], dl2[3], pl1[3], pl2[3], a[3], b[3];
   rotvecT(dl1, g1.mat, dir); rotvecT(dl2, g2.mat, nd);
-  cvx_support_local(g1, dl1, pl1); cvx_support_local(g2, dl2, pl2);
-  mesh_support_wave(act && g1.type == MJH_GEOM_MESH, g1.vert, g1.nvert, dl1, pl1, lane);
-  mesh_support_wave(act && g2.type == MJH_GEOM_MESH, g2.vert, g2.nvert, dl2, pl2, lane);
+  if constexpr (PRISM) prism_support_local(*h, dl1, pl1); else cvx_support_local(g1, dl1, pl1);
+  cvx_support_local(g2, dl2, pl2);
+  if constexpr (!PRISM) mesh_support_wave(act && g1.type == MJH_GEOM_MESH, g1.vert, g1.nvert, dl1, pl1, lane);
+  // prisms of one height-field pair: every lane holds the SAME mesh (g2 uniform), so each lane scans the hull itself — the loads
+  // are the same addresses on every lane (broadcast), and no lane waits for the other lanes' requests to be served
+  if constexpr (PRISM) { if (g2.type == MJH_GEOM_MESH) mesh_support_lane(g2.vert, g2.nvert, dl2, pl2); }
+  else mesh_support_wave(act && g2.type == MJH_GEOM_MESH, g2.vert, g2.nvert, dl2, pl2, lane);
   rotvec(a, g1.mat, pl1); rotvec(b, g2.mat, pl2);
 #pragma unroll
   for (int k = 0; k < 3; k++) {
@@ -140,7 +170,8 @@ DEV void mpr_support_wave(const CvxGeom& g1, const CvxGeom& g2, const float* dir
 // The five places of the algorithm that ask for a support point (first and second portal vertex, portal discovery, refinement,
 // push to the surface) share ONE support evaluation per trip of a phase loop: lanes that are in different phases still evaluate
 // their support mappings together, and the wave leaves the loop when its last pair is decided.
-DEV int c_convex_wave(CvxGeom& g1, CvxGeom& g2, float margin, float* st, const bool act, const int lane) {
+template <bool PRISM = false>
+DEV int c_convex_wave(CvxGeom& g1, CvxGeom& g2, float margin, float* st, const bool act, const int lane, const HfPrism* h = nullptr) {
   g1.pad = g2.pad = 0.5f * margin;
   MprPt p0, p1, p2, p3, p4;
   float n[3], c[3];
@@ -154,7 +185,7 @@ DEV int c_convex_wave(CvxGeom& g1, CvxGeom& g2, float margin, float* st, const b
   bool live = act;          // still iterating
   int res = 0;              // 0: no contact, 1: contact emitted on the ray p0 -> p1, 2: contact from the final portal
   while (__ballot(live) != 0) {
-    mpr_support_wave(g1, g2, n, p4, live, lane);
+    mpr_support_wave<PRISM>(g1, g2, n, p4, live, lane, h);
     if (live) {
     const float d4 = dot3(p4.v, n);
     if (phase == PH_FIRST) {

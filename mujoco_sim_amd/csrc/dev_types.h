@@ -112,7 +112,11 @@ struct Lay {
   int g_dense;   // dense solver: AR' [cap x cap] | B rows [cap x nvs] | J rows [cap x nvs] | f, lo, hi, AR_qq, t, row map [6 x cap]
 };
 
-struct DConst { DModel M; Lay L; };
+// height fields (read by the HF kernel instances only; behind L so that the other instances' offsets into DConst stay as they were):
+// int tables nrow / ncol / adr per hfield, float tables size [4 per hfield] and the normalised elevations, all in the shared I / F buffers
+struct DHField { int has_hfield, o_hfield_nrow, o_hfield_ncol, o_hfield_adr, o_hfield_size, o_hfield_data; };
+
+struct DConst { DModel M; Lay L; DHField H; };
 
 // kernel phases
 enum { PH_STEP1 = 1, PH_INV = 2, PH_STEP2 = 4, PH_NOINT = 8, PH_FKONLY = 16, PH_MULM = 32, PH_RESET = 64,

@@ -19,6 +19,10 @@
 void mjh_set_error(const std::string& s);  // model_builder.cpp
 hipError_t mjh_launch_window(hipStream_t st, int nvt, int grid, size_t lds, const DConst* dC, const DState& S, int env0, int n, int nl, int wxf, int n32, int n64);   // window.hip
 hipError_t mjh_dense_attributes(size_t build_lds, size_t solve_lds);   // dense.hip (kernels of dense_pgs.h)
+// hfield.hip: the step kernel's instances for models with height-field pairs (every layout) and their LDS ceilings
+hipError_t mjh_launch_step_hf(hipStream_t st, int nr, bool diag, int wpre, int grid, size_t lds, const DConst* dC, const DState& S,
+                              int env0, int nsteps, int ph, int xflags);
+hipError_t mjh_step_hf_attributes(size_t lds);
 hipError_t mjh_launch_dense(hipStream_t st, int n, size_t build_lds, size_t solve_lds, const DConst* dC, const DState& S, int env0);
 #define DN_CAP_MAX 256          // row capacity of the dense solver (dense_pgs.h)
 
@@ -60,6 +64,7 @@ struct mjh_engine {
   DState S{};
   Lay L{};
   int lds_bytes = 0, lds_bytes_pre = 0;   // dynamic LDS per env of the step kernel; ... of its assemble-only instance (no patch pool: more envs per CU)
+  DHField H{};                            // height fields (H.has_hfield: every launch of the step kernel takes an HF instance, hfield.hip)
   size_t dense_lds = 0, dense_solve_lds = 0;   // dynamic LDS of mjh_dense_build_kernel / mjh_dense_solve_kernel
   // dense solver on / off per cohort: mjh_order_kernel leaves "an env of the cohort swept long" in a host-mapped word (four slots per
   // cohort, one per rebuild of the launch order); the host adopts the word of TWO rebuilds ago after waiting for that kernel's event
@@ -159,7 +164,8 @@ static int launch_on(mjh_engine* e, hipStream_t st, int env0, int n, int nsteps,
   if (wmode && !window) { mjh_set_error("internal: window-chain launch mode on a launch that is not one"); return MJH_ERR_STATE; }
   if (wmode == 1) xflags |= XF_DEFER;
   if (wmode != 2) {
-#define MJH_LAUNCH2(NR, DG, CX) hipLaunchKernelGGL((mjh_step_kernel<NR, DG, CX>), dim3(n), dim3(64), (size_t)e->lds_bytes, st, e->dC, e->S, env0, nsteps, ph, xflags)
+#define MJH_LAUNCH2(NR, DG, CX) do { if (e->H.has_hfield) HIPCHK(mjh_launch_step_hf(st, NR, DG, 0, n, (size_t)e->lds_bytes, e->dC, e->S, env0, nsteps, ph, xflags)); \
+                                   else hipLaunchKernelGGL((mjh_step_kernel<NR, DG, CX>), dim3(n), dim3(64), (size_t)e->lds_bytes, st, e->dC, e->S, env0, nsteps, ph, xflags); } while (0)
 #define MJH_LAUNCH(NR, DG) do { if (extra_instance(e->M) || e->S.xfrc_applied) MJH_LAUNCH2(NR, DG, true); else MJH_LAUNCH2(NR, DG, false); } while (0)
   const int nr = e->M.big ? 8 : (e->M.nv <= 16 ? 1 : (e->M.nv <= 32 ? 2 : 4));   // 8: many-body layout, running acceleration in LDS
   static const bool slim = !(getenv("MJH_WINDOW_SLIM") && atoi(getenv("MJH_WINDOW_SLIM")) == 0);
@@ -171,7 +177,8 @@ static int launch_on(mjh_engine* e, hipStream_t st, int env0, int n, int nsteps,
     static const int wpad = getenv("MJH_WPRE_LDS_PAD") ? std::max(0, atoi(getenv("MJH_WPRE_LDS_PAD"))) : 0;      // (occupancy experiments: bytes of unused LDS per assemble-only workgroup)
     const size_t wlds = (size_t)((slim_lds && e->lds_bytes_pre > 0) ? e->lds_bytes_pre : e->lds_bytes) + (size_t)wpad;
     // (models of up to 64 contacts keep the base-row pool in LDS — instance 1 —, larger ones in the env's window slice — instance 2: derive_device_model)
-#define MJH_LAUNCHW(NR, CX, GJ) hipLaunchKernelGGL((mjh_step_kernel<NR, true, CX, GJ>), dim3(n), dim3(64), wlds, st, e->dC, e->S, env0, nsteps, ph, xflags)
+#define MJH_LAUNCHW(NR, CX, GJ) do { if (e->H.has_hfield) HIPCHK(mjh_launch_step_hf(st, NR, true, GJ, n, wlds, e->dC, e->S, env0, nsteps, ph, xflags)); \
+                                   else hipLaunchKernelGGL((mjh_step_kernel<NR, true, CX, GJ>), dim3(n), dim3(64), wlds, st, e->dC, e->S, env0, nsteps, ph, xflags); } while (0)
 #define MJH_LAUNCHW2(NR, CX) do { if (e->M.patch) MJH_LAUNCHW(NR, CX, 1); else MJH_LAUNCHW(NR, CX, 2); } while (0)
     if (nr == 1) { if (cx) MJH_LAUNCHW2(1, true); else MJH_LAUNCHW2(1, false); } else { if (cx) MJH_LAUNCHW2(2, true); else MJH_LAUNCHW2(2, false); }
 #undef MJH_LAUNCHW2
@@ -237,12 +244,13 @@ static int pair_cap(int t1, int t2) {
   if (t1 == MJH_GEOM_PLANE && t2 == MJH_GEOM_CYLINDER) return 4;
   if (t1 == MJH_GEOM_PLANE && t2 == MJH_GEOM_MESH) return 4;
   if (t1 == MJH_GEOM_BOX && t2 == MJH_GEOM_BOX) return 8;
+  if (t1 == MJH_GEOM_HFIELD) return MJH_HFIELD_MAXCON;       // (hfield-x: raw staging of the pair's first contacts in prism order)
   return 1;
 }
 
 // Host-only derivation of the device model: packed tables, derived topology tables, capacities and the LDS
 // layout.  Needs no HIP device (mjh_query_lds_bytes uses it for capacity planning and in the CPU tests).
-struct HostPack { DModel M{}; Lay L{}; std::vector<int> I; std::vector<float> F; int o_controlled = 0, o_odom = 0, lds_bytes = 0, lds_bytes_pre = 0; long long gstride = 0; };
+struct HostPack { DModel M{}; Lay L{}; DHField H{}; std::vector<int> I; std::vector<float> F; int o_controlled = 0, o_odom = 0, lds_bytes = 0, lds_bytes_pre = 0; long long gstride = 0; };
 // Gauss-Seidel order of engines created afterwards (mjhip.h): 1 = mj_solPGS's own row order
 #define MJH_WINDOW_MAXCON 128    // contact capacity up to which a small free-body model steps through the window chain
 static int g_window_solver = getenv("MJH_WINDOW") ? (atoi(getenv("MJH_WINDOW")) != 0) : 1;
@@ -328,6 +336,15 @@ static void derive_device_model(const mjh_model* m, HostPack& hp, bool force_big
     M.o_body_mocapid = addI(mocapid.data(), nb);
   }
   M.nsite = m->nsite; M.nsensor = m->nsensor; M.nmocap = m->nmocap; M.has_weld = has_weld ? 1 : 0;
+  {   // height fields: packed behind every other table (models without hfield pairs keep their tables exactly)
+    DHField& H = hp.H;
+    H.has_hfield = 0;
+    for (int i = 0; i < m->npair; i++) if (m->geom_type[m->pair_geom1[i]] == MJH_GEOM_HFIELD) H.has_hfield = 1;
+    if (H.has_hfield) {
+      H.o_hfield_nrow = addI(m->hfield_nrow, m->nhfield); H.o_hfield_ncol = addI(m->hfield_ncol, m->nhfield); H.o_hfield_adr = addI(m->hfield_adr, m->nhfield);
+      H.o_hfield_size = addF(m->hfield_size, 4 * (size_t)m->nhfield); H.o_hfield_data = addF(m->hfield_data, (size_t)m->nhfielddata);
+    }
+  }
   // groups of up to 16 mutually independent blocks (four waves x four 16-lane rows in mjh_solve_kernel) when a tree bitmask fits
   // one 64-bit word and every block fits a 16-lane row; else 4 (same rule as the oracle's m_group_max)
   M.group_max = m->ntree <= 64 ? 16 : 4;
@@ -600,7 +617,7 @@ extern "C" int mjh_create(const mjh_model* m, int nenv, int device, void* stream
   e->model = m; e->nenv = nenv; e->device = device; e->stream = (hipStream_t)stream;
 
   HostPack hp; derive_fitting(m, hp);
-  e->M = hp.M; e->L = hp.L; e->lds_bytes = hp.lds_bytes; e->lds_bytes_pre = hp.lds_bytes_pre; e->o_controlled = hp.o_controlled; e->o_odom = hp.o_odom;
+  e->M = hp.M; e->L = hp.L; e->H = hp.H; e->lds_bytes = hp.lds_bytes; e->lds_bytes_pre = hp.lds_bytes_pre; e->o_controlled = hp.o_controlled; e->o_odom = hp.o_odom;
   DModel& M = e->M; std::vector<int>& I = hp.I; std::vector<float>& F = hp.F;
   e->hI = I;
   if (dev_alloc(e, &e->dI, I.size(), false) || dev_alloc(e, &e->dF, F.size(), false)) { mjh_destroy(e); return MJH_ERR_NO_DEVICE; }
@@ -610,7 +627,7 @@ extern "C" int mjh_create(const mjh_model* m, int nenv, int device, void* stream
   M.I = e->dI; M.F = e->dF;
 
   {
-    DConst hc; hc.M = e->M; hc.L = e->L;
+    DConst hc; hc.M = e->M; hc.L = e->L; hc.H = e->H;
     if (dev_alloc(e, &e->dC, 1, false)) { mjh_destroy(e); return MJH_ERR_NO_DEVICE; }
     HIPCHK(hipMemcpyAsync(e->dC, &hc, sizeof hc, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
@@ -642,6 +659,7 @@ extern "C" int mjh_create(const mjh_model* m, int nenv, int device, void* stream
   }
   MJH_ATTR(1, true); MJH_ATTR(2, true); MJH_ATTR(4, true); MJH_ATTR(8, true); MJH_ATTR(1, false); MJH_ATTR(2, false); MJH_ATTR(4, false); MJH_ATTR(8, false);
 #undef MJH_ATTR
+  if (e->H.has_hfield) HIPCHK(mjh_step_hf_attributes((size_t)e->lds_bytes));
   if (e->M.window) {
 #define MJH_ATTRW(NR, CX, GJ) HIPCHK(hipFuncSetAttribute((const void*)mjh_step_kernel<NR, true, CX, GJ>, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes))
     MJH_ATTRW(1, false, 1); MJH_ATTRW(1, true, 1); MJH_ATTRW(2, false, 1); MJH_ATTRW(2, true, 1);

@@ -5,8 +5,11 @@
 // <freejoint>, <geom> (plane, sphere, capsule, cylinder, box, ellipsoid, mesh: binary / ASCII STL and OBJ assets become convex hulls), gravcomp,
 // <contact><exclude>, <equality><joint polycoef> / <weld> / <connect>, <body mocap>, <site>, <sensor><force> / <torque>.  Everything is translated into mjh_builder_* calls; physics
 // defaults follow MuJoCo's documented defaults (angle = degree, hinge axis 0 0 1, geom type sphere, ...).
-// Not handled (reported in the returned note, mjh_load_note): tendons, actuators, height fields, sensors other than force / torque.
+// <asset><hfield> (inline elevation or MuJoCo's binary file; PNG files are skipped with their geoms) and hfield geoms on static bodies.
+// Not handled (reported in the returned note, mjh_load_note): tendons, actuators, PNG height fields, sensors other than force / torque.
+#include <cctype>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -115,7 +118,7 @@ struct Loader {
   int nfiles = 1;                    // files of this load (mjh_load_mjcf_files): a single file is treated as the robot file by the per-robot rules that say so
   double bmass = 0, binertia = 0;   // <compiler boundmass boundinertia>, raised to the process-wide floor of mjh_load_set_bounds
   Defaults def;
-  std::map<std::string, int> body_id, joint_id, mesh_id, site_id;
+  std::map<std::string, int> body_id, joint_id, mesh_id, site_id, hfield_id;
   std::vector<int> body_parent;      // parent body of every body added so far
   // <default class="..."> tables: class -> element tag -> attributes (a nested class starts from its parent's); the
   // unnamed top-level <default> is class "main".  An element takes the attributes it does not set itself from its class
@@ -160,7 +163,7 @@ struct Loader {
     }
     return false;
   }
-  void geom(const Node& n0, int body) {
+  bool geom(const Node& n0, int body) {
     const Node n = with_defaults(n0);
     const char* type = n.get("type");
     int gt = MJH_GEOM_SPHERE;
@@ -168,8 +171,8 @@ struct Loader {
       std::string t = type;
       if (t == "plane") gt = MJH_GEOM_PLANE; else if (t == "sphere") gt = MJH_GEOM_SPHERE; else if (t == "capsule") gt = MJH_GEOM_CAPSULE;
       else if (t == "cylinder") gt = MJH_GEOM_CYLINDER; else if (t == "box") gt = MJH_GEOM_BOX; else if (t == "ellipsoid") gt = MJH_GEOM_ELLIPSOID;
-      else if (t == "mesh") gt = MJH_GEOM_MESH;
-      else { note += "skipped <geom type=\"" + t + "\">; "; return; }
+      else if (t == "mesh") gt = MJH_GEOM_MESH; else if (t == "hfield") gt = MJH_GEOM_HFIELD;
+      else { note += "skipped <geom type=\"" + t + "\">; "; return true; }
     } else if (n.get("mesh")) gt = MJH_GEOM_MESH;
     double size[3] = {0, 0, 0}, pos[3] = {0, 0, 0}, quat[4] = {1, 0, 0, 0}, fr[3];
     nums(n.get("size"), size, 3); nums(n.get("pos"), pos, 3); orientation(n, quat);
@@ -177,7 +180,7 @@ struct Loader {
     if (nums(n.get("fromto"), ft, 6) == 6) {
       // fromto: the geom's z axis runs from the first point to the second; size = radius (capsule, cylinder) or the two
       // lateral half-sizes (box, ellipsoid), the half-length comes from the distance
-      if (gt != MJH_GEOM_CAPSULE && gt != MJH_GEOM_CYLINDER && gt != MJH_GEOM_BOX && gt != MJH_GEOM_ELLIPSOID) { note += "skipped <geom fromto> of this type; "; return; }
+      if (gt != MJH_GEOM_CAPSULE && gt != MJH_GEOM_CYLINDER && gt != MJH_GEOM_BOX && gt != MJH_GEOM_ELLIPSOID) { note += "skipped <geom fromto> of this type; "; return true; }
       double d[3] = {ft[3] - ft[0], ft[4] - ft[1], ft[5] - ft[2]};
       const double len = hm::norm3(d);
       for (int k = 0; k < 3; k++) pos[k] = 0.5 * (ft[k] + ft[3 + k]);
@@ -201,11 +204,17 @@ struct Loader {
     if (nums(n.get("density"), &v, 1)) density = v;
     if (gt == MJH_GEOM_MESH) {
       auto it = mesh_id.find(n.get("mesh") ? n.get("mesh") : "");
-      if (it == mesh_id.end()) { note += std::string("skipped mesh geom (mesh ") + (n.get("mesh") ? n.get("mesh") : "?") + " not loaded); "; return; }
+      if (it == mesh_id.end()) { note += std::string("skipped mesh geom (mesh ") + (n.get("mesh") ? n.get("mesh") : "?") + " not loaded); "; return true; }
       mjh_builder_add_mesh_geom(b, n.get("name"), body, it->second, pos, quat, fr, condim, contype, conaff, density);
-      return;
+      return true;
+    }
+    if (gt == MJH_GEOM_HFIELD) {      // (the geom's size is ignored: the asset's size sets the terrain)
+      auto it = hfield_id.find(n.get("hfield") ? n.get("hfield") : "");
+      if (it == hfield_id.end()) { note += std::string("skipped hfield geom (hfield ") + (n.get("hfield") ? n.get("hfield") : "?") + " not loaded); "; return true; }
+      return mjh_builder_add_hfield_geom(b, n.get("name"), body, it->second, pos, quat, fr, condim, contype, conaff) >= 0;
     }
     mjh_builder_add_geom(b, n.get("name"), body, gt, size, pos, quat, fr, condim, contype, conaff, density);
+    return true;
   }
   bool joint(const Node& n0, int body, bool freejoint) {
     const Node n = freejoint ? with_defaults(Node()) : with_defaults(n0);
@@ -283,7 +292,7 @@ struct Loader {
   }
   bool children(const Node& n, int body) {
     for (auto& c : n.kids) {
-      if (c->tag == "geom") geom(*c, body);
+      if (c->tag == "geom") { if (!geom(*c, body)) return false; }
       else if (c->tag == "body") { if (!this->body(*c, body)) return false; }
       else if (c->tag == "joint" || c->tag == "freejoint") {
         if (body == 0) { mjh_set_error("joint in worldbody"); return false; }
@@ -311,7 +320,7 @@ struct Loader {
     if (root.tag != "mujoco") { mjh_set_error("root element must be <mujoco>"); return false; }
     if (first) b = mjh_builder_create();
     robot_file = !first;      // files after the world file are robots (MjSim::init composition)
-    degree = true; autolimits = false; def = Defaults(); basedir = dir; meshdir.clear(); mesh_id.clear(); classes.clear(); childclass.clear();
+    degree = true; autolimits = false; def = Defaults(); basedir = dir; meshdir.clear(); mesh_id.clear(); hfield_id.clear(); classes.clear(); childclass.clear();
     mjh_option o; mjh_builder_get_option(b, &o);
     bool solver_named = false;
     // first pass: compiler / option / default (they may appear after worldbody in a file)
@@ -380,6 +389,47 @@ struct Loader {
       const int id = mjh_builder_add_mesh_stl(b, path.c_str(), sc);
       if (id < 0) { note += "mesh " + name + " not loaded (" + mjh_last_error() + "); "; continue; }
       mesh_id[name] = id;
+    }
+    // <asset><hfield>: inline (nrow ncol [elevation]) or MuJoCo's binary file (int32 nrow, int32 ncol, float32 data[nrow*ncol]),
+    // resolved as mesh files are; PNG files are skipped (no image decoder), and with them the geoms that use them
+    for (auto& c : root.kids) if (c->tag == "asset") for (auto& a : c->kids) if (a->tag == "hfield") {
+      std::string name = a->get("name") ? a->get("name") : "";
+      double size[4] = {0, 0, 0, 0};
+      nums(a->get("size"), size, 4);
+      int nrow = 0, ncol = 0;
+      std::vector<double> elev;
+      if (const char* file = a->get("file")) {
+        std::string fn = file;
+        if (name.empty()) { size_t sl = fn.find_last_of('/'), dot = fn.find_last_of('.'); name = fn.substr(sl == std::string::npos ? 0 : sl + 1, dot == std::string::npos ? std::string::npos : dot - (sl == std::string::npos ? 0 : sl + 1)); }
+        std::string ext = fn.size() >= 4 ? fn.substr(fn.size() - 4) : "";
+        for (char& ch : ext) ch = (char)std::tolower((unsigned char)ch);
+        if (ext == ".png") { note += "hfield " + name + " not loaded (PNG elevation files are not supported); "; continue; }
+        if (basedir.empty() && fn[0] != '/') { note += "hfield " + name + " not loaded (MJCF given as a string: no directory); "; continue; }
+        const std::string path = fn[0] == '/' ? fn : basedir + meshdir + fn;
+        FILE* f = std::fopen(path.c_str(), "rb");
+        if (!f) { mjh_set_error("hfield " + name + ": cannot open " + path); return false; }
+        int32_t hdr[2] = {0, 0};
+        const bool ok = std::fread(hdr, sizeof(int32_t), 2, f) == 2 && hdr[0] >= 2 && hdr[1] >= 2 && (long long)hdr[0] * hdr[1] <= (1LL << 24);
+        std::vector<float> buf(ok ? (size_t)hdr[0] * hdr[1] : 0);
+        const bool full = ok && std::fread(buf.data(), sizeof(float), buf.size(), f) == buf.size();
+        std::fclose(f);
+        if (!full) { mjh_set_error("hfield " + name + ": " + path + " is not a binary height field (int32 nrow, int32 ncol, float32 data)"); return false; }
+        nrow = hdr[0]; ncol = hdr[1]; elev.assign(buf.begin(), buf.end());
+      } else {
+        double v;
+        if (nums(a->get("nrow"), &v, 1)) nrow = (int)v;
+        if (nums(a->get("ncol"), &v, 1)) ncol = (int)v;
+        if (nrow >= 2 && ncol >= 2 && (long long)nrow * ncol <= (1LL << 24)) {
+          elev.assign((size_t)nrow * ncol + 1, 0.0);       // (one more slot: a longer list is an error too, as in MuJoCo)
+          if (a->get("elevation") && nums(a->get("elevation"), elev.data(), nrow * ncol + 1) != nrow * ncol) {
+            mjh_set_error("hfield " + name + ": elevation needs nrow*ncol = " + std::to_string(nrow * ncol) + " values"); return false;
+          }
+          elev.pop_back();
+        }
+      }
+      const int id = mjh_builder_add_hfield(b, name.c_str(), nrow, ncol, size, elev.empty() ? nullptr : elev.data());
+      if (id < 0) { mjh_set_error("hfield " + name + ": " + mjh_last_error()); return false; }
+      hfield_id[name] = id;
     }
     const int body_first = std::max(1, (int)body_parent.size());      // first body this file adds
     for (auto& c : root.kids) if (c->tag == "worldbody") if (!children(*c, 0)) return false;

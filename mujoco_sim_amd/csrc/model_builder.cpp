@@ -31,8 +31,10 @@ struct BJoint {
 };
 struct BGeom {
   std::string name; int body, type; double size[3], pos[3], quat[4], friction[3];
-  int condim, contype, conaffinity; double density; int mesh = -1;
+  int condim, contype, conaffinity; double density; int mesh = -1; int hfield = -1;
 };
+// height field asset: elevation grid as given (normalised at compile time)
+struct BHField { std::string name; int nrow, ncol; double size[4]; std::vector<double> data; };
 // convex mesh asset in its own frame: origin = centre of mass, axes = principal axes of inertia
 struct BMesh {
   std::vector<double> vert;        // support-relevant vertices, own frame
@@ -56,6 +58,7 @@ struct mjh_builder {
   std::vector<BJoint> joints;
   std::vector<BGeom> geoms;
   std::vector<BMesh> meshes;
+  std::vector<BHField> hfields;
   std::vector<std::pair<int,int>> excludes;
   std::vector<BEq> eqs;
   std::vector<BSite> sites;
@@ -362,6 +365,39 @@ extern "C" int mjh_builder_add_mesh_geom(mjh_builder* b, const char* name, int b
   return g;
 }
 
+extern "C" int mjh_builder_add_hfield(mjh_builder* b, const char* name, int nrow, int ncol, const double size[4], const double* elevation) {
+  if (!b || !size) { g_err = "add_hfield: bad arguments"; return MJH_ERR_ARG; }
+  if (nrow < 2 || ncol < 2) { g_err = "add_hfield: nrow and ncol must be at least 2"; return MJH_ERR_ARG; }
+  if ((long long)nrow * ncol > (1LL << 24)) { g_err = "add_hfield: grid too large"; return MJH_ERR_ARG; }
+  for (int k = 0; k < 4; k++) if (!(size[k] > 0)) { g_err = "add_hfield: every size entry (radius_x radius_y elevation_z base_z) must be > 0"; return MJH_ERR_ARG; }
+  BHField h; h.name = name ? name : ""; h.nrow = nrow; h.ncol = ncol;
+  for (int k = 0; k < 4; k++) h.size[k] = size[k];
+  h.data.assign((size_t)nrow * ncol, 0.0);
+  if (elevation) for (size_t i = 0; i < h.data.size(); i++) {
+    if (!std::isfinite(elevation[i])) { g_err = "add_hfield: elevation is not finite"; return MJH_ERR_ARG; }
+    h.data[i] = elevation[i];
+  }
+  b->hfields.push_back(std::move(h));
+  return (int)b->hfields.size() - 1;
+}
+extern "C" int mjh_builder_add_hfield_geom(mjh_builder* b, const char* name, int body, int hfield, const double pos[3], const double quat[4],
+                                           const double friction[3], int condim, int contype, int conaffinity) {
+  if (!b || hfield < 0 || hfield >= (int)b->hfields.size()) { g_err = "add_hfield_geom: bad hfield id"; return MJH_ERR_ARG; }
+  if (body < 0 || body >= (int)b->bodies.size()) { g_err = "add_hfield_geom: bad body"; return MJH_ERR_ARG; }
+  for (int a = body; a > 0; a = b->bodies[a].parent) {      // static: neither the body nor an ancestor has a joint
+    for (const BJoint& j : b->joints) if (j.body == a) {
+      g_err = "add_hfield_geom: height fields are supported on static bodies only (body '" + b->bodies[body].name + "' moves)";
+      return MJH_ERR_UNSUPPORTED;
+    }
+    for (int mb : b->mocap) if (mb == a) { g_err = "add_hfield_geom: height fields are not supported on mocap bodies"; return MJH_ERR_UNSUPPORTED; }
+  }
+  const BHField& H = b->hfields[hfield];
+  const double size[3] = {H.size[0], H.size[1], H.size[2]};
+  const int g = mjh_builder_add_geom(b, name, body, MJH_GEOM_HFIELD, size, pos, quat, friction, condim, contype, conaffinity, 0.0);
+  if (g >= 0) b->geoms[g].hfield = hfield;
+  return g;
+}
+
 extern "C" int mjh_builder_add_exclude(mjh_builder* b, int b1, int b2) { b->excludes.push_back({b1, b2}); return MJH_OK; }
 extern "C" int mjh_builder_add_eq_joint(mjh_builder* b, int j1, int j2, const double poly[5]) {
   BEq e; e.j1 = j1; e.j2 = j2; for (int i = 0; i < 5; i++) e.poly[i] = poly[i];
@@ -448,6 +484,7 @@ static double geom_rbound(int type, const double* s) {
     case MJH_GEOM_BOX: return std::sqrt(s[0]*s[0] + s[1]*s[1] + s[2]*s[2]);
     case MJH_GEOM_ELLIPSOID: return std::max(s[0], std::max(s[1], s[2]));
     case MJH_GEOM_MESH: return s[0];   // size[0] of a mesh geom = bounding radius of its vertices about the centre of mass
+    // (hfield: set from its asset at compile time — the box x, y in +-radius, z in [-base, elevation])
     default: return 0;  // plane: unbounded, handled by the pair routine
   }
 }
@@ -457,8 +494,8 @@ extern "C" double mjh_geom_rbound(int type, const double* size) { return geom_rb
 static bool pair_supported(int t1, int t2) {
   if (t1 > t2) std::swap(t1, t2);
   auto is = [](int t, int a) { return t == a; };
-  if (is(t1, MJH_GEOM_HFIELD) || is(t2, MJH_GEOM_HFIELD)) return false;
-  if (is(t1, MJH_GEOM_PLANE)) return t2 != MJH_GEOM_PLANE;
+  if (is(t1, MJH_GEOM_PLANE)) return t2 != MJH_GEOM_PLANE && t2 != MJH_GEOM_HFIELD;   // (plane-hfield, hfield-hfield: no routine)
+  if (is(t1, MJH_GEOM_HFIELD)) return t2 != MJH_GEOM_HFIELD;
   return true;   // analytic routine, or the generic convex narrow phase (cylinder-x, capsule-box, ellipsoid-x, mesh-x)
 }
 static int pair_maxcon(int t1, int t2) {
@@ -468,6 +505,7 @@ static int pair_maxcon(int t1, int t2) {
   if (t1 == MJH_GEOM_PLANE && t2 == MJH_GEOM_CYLINDER) return 4;
   if (t1 == MJH_GEOM_PLANE && t2 == MJH_GEOM_MESH) return 4;
   if (t1 == MJH_GEOM_BOX && t2 == MJH_GEOM_BOX) return 8;
+  if (t1 == MJH_GEOM_HFIELD) return MJH_HFIELD_MAXCON;
   return 1;
 }
 
@@ -590,6 +628,12 @@ extern "C" mjh_model* mjh_builder_compile(mjh_builder* B) {
     for (int k = 0; k < 4; k++) geom_quat[4*g+k] = G.quat[k];
     geom_rb[g] = geom_rbound(G.type, G.size);
     geom_dataid[g] = G.type == MJH_GEOM_MESH ? G.mesh : -1;
+    if (G.type == MJH_GEOM_HFIELD && G.hfield >= 0) {
+      const double* hs = B->hfields[G.hfield].size;
+      if (body_weldid[newid[G.body]] != 0) { g_err = "hfield geom '" + G.name + "': height fields are supported on static bodies only"; return nullptr; }
+      geom_dataid[g] = G.hfield;
+      geom_rb[g] = std::sqrt(hs[0]*hs[0] + hs[1]*hs[1] + std::max(hs[2], hs[3])*std::max(hs[2], hs[3]));
+    }
     geom_solmix[g] = 1; geom_solref[2*g] = 0.02; geom_solref[2*g+1] = 1;
     const double si[5] = {0.9, 0.95, 0.001, 0.5, 2};
     for (int k = 0; k < 5; k++) geom_solimp[5*g+k] = si[k];
@@ -850,6 +894,7 @@ extern "C" mjh_model* mjh_builder_compile(mjh_builder* B) {
     if (!((geom_contype[g1] & geom_conaffinity[g2]) || (geom_contype[g2] & geom_conaffinity[g1]))) continue;
     if (excluded(b1, b2)) continue;
     if (!pair_supported(geom_type[g1], geom_type[g2])) continue;
+    if ((geom_type[g1] == MJH_GEOM_HFIELD && geom_dataid[g1] < 0) || (geom_type[g2] == MJH_GEOM_HFIELD && geom_dataid[g2] < 0)) continue;   // hfield geom without an asset
     P p; p.b1 = std::min(b1, b2); p.b2 = std::max(b1, b2);
     if (geom_type[g1] <= geom_type[g2]) { p.g1 = g1; p.g2 = g2; } else { p.g1 = g2; p.g2 = g1; }
     pairs.push_back(p);
@@ -928,6 +973,20 @@ extern "C" mjh_model* mjh_builder_compile(mjh_builder* B) {
   m->nmesh = (int)mesh_vertadr.size(); m->nmeshvert = (int)mesh_vert.size() / 3;
   SETI(geom_dataid); SETI(mesh_vertadr); SETI(mesh_vertnum); SETI(mesh_vert);
 #undef SETI
+  {   // height fields: elevation normalised to [0, 1] (minus the minimum, divided by the range when it is non-zero)
+    const int nh = (int)B->hfields.size();
+    std::vector<int> nrow(nh), ncol(nh), adr(nh); std::vector<double> size(4 * (size_t)nh), data; std::vector<std::string> names(nh);
+    for (int h = 0; h < nh; h++) {
+      const BHField& H = B->hfields[h];
+      nrow[h] = H.nrow; ncol[h] = H.ncol; adr[h] = (int)data.size(); names[h] = H.name;
+      for (int k = 0; k < 4; k++) size[4*h+k] = H.size[k];
+      const double lo = *std::min_element(H.data.begin(), H.data.end()), hi = *std::max_element(H.data.begin(), H.data.end());
+      for (double v : H.data) data.push_back(hi > lo ? (v - lo) / (hi - lo) : v - lo);
+    }
+    m->nhfield = nh; m->nhfielddata = (int)data.size();
+    m->hfield_nrow = dup(nrow); m->hfield_ncol = dup(ncol); m->hfield_adr = dup(adr); m->hfield_size = dup(size); m->hfield_data = dup(data);
+    m->hfield_names = dupnames(names);
+  }
   m->body_names = dupnames(body_names); m->jnt_names = dupnames(jnt_names); m->geom_names = dupnames(geom_names);
   {   // sites, force / torque sensors, mocap bodies
     const int nsite = (int)B->sites.size(), nsensor = (int)B->sensors.size();
@@ -956,6 +1015,7 @@ extern "C" mjh_model* mjh_builder_compile(mjh_builder* B) {
 extern "C" mjh_model* mjh_model_replicate(const mjh_model* a, int G) {
   if (!a || G < 1) { g_err = "mjh_model_replicate: bad arguments"; return nullptr; }
   if (a->nsite || a->nsensor || a->nmocap) { g_err = "mjh_model_replicate: models with sites, sensors or mocap bodies are not packed"; return nullptr; }
+  if (a->nhfield > 0) { g_err = "mjh_model_replicate: models with height fields are not packed"; return nullptr; }
   for (int e = 0; e < a->neq; e++) if (a->eq_type[e] != MJH_EQ_JOINT) { g_err = "mjh_model_replicate: connect / weld equalities are not packed"; return nullptr; }
   const int nb = a->nbody, nj = a->njnt, nv = a->nv, nq = a->nq, ng = a->ngeom, nt = a->ntree, ne = a->neq, np = a->npair, nM = a->nM;
   std::vector<int> moving_b, moving_g;
@@ -1082,11 +1142,12 @@ extern "C" void mjh_model_destroy(mjh_model* m) {
     m->geom_size, m->geom_rbound, m->geom_friction, m->geom_solmix, m->geom_solref, m->geom_solimp, m->geom_margin, m->geom_gap,
     m->pair_geom1, m->pair_geom2, m->eq_type, m->eq_obj1id, m->eq_obj2id, m->eq_active, m->eq_data, m->eq_solref, m->eq_solimp,
     m->geom_dataid, m->mesh_vertadr, m->mesh_vertnum, m->mesh_vert,
-    m->site_bodyid, m->site_pos, m->site_quat, m->sensor_type, m->sensor_objid, m->sensor_adr, m->body_mocapid};
+    m->site_bodyid, m->site_pos, m->site_quat, m->sensor_type, m->sensor_objid, m->sensor_adr, m->body_mocapid,
+    m->hfield_nrow, m->hfield_ncol, m->hfield_adr, m->hfield_size, m->hfield_data};
   for (void* p : ptrs) std::free(p);
   auto freen = [](char** n, int c) { if (!n) return; for (int i = 0; i < c; i++) std::free(n[i]); std::free(n); };
   freen(m->body_names, m->nbody); freen(m->jnt_names, m->njnt); freen(m->geom_names, m->ngeom);
-  freen(m->site_names, m->nsite); freen(m->sensor_names, m->nsensor);
+  freen(m->site_names, m->nsite); freen(m->sensor_names, m->nsensor); freen(m->hfield_names, m->nhfield);
   std::free(m);
 }
 

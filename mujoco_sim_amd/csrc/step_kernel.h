@@ -925,7 +925,9 @@ DEV int pgs_many_body(const ManyCtx& c, const int lane) {
 
 // WPRE: 0 the whole kernel; assemble-only instances of the window chain (no sweep code): 1 with the base-row pool in LDS, 2 with the pool in the
 // env's window slice (models beyond 64 contacts: the pool is what decides how many envs a CU holds)
-template <int NROW, bool DIAGM, bool EXTRA, int WPRE = 0>
+// HF: the model has height-field pairs (instances of their own, compiled in hfield.hip, EXTRA set): the collision stage adds the prism narrow
+// phase; every other instance compiles exactly as before
+template <int NROW, bool DIAGM, bool EXTRA, int WPRE = 0, bool HF = false>
 #ifndef MJH_STEP_WAVES
 // resident waves per SIMD the register allocation aims at: two for the instances that keep sweep records in registers (free-body
 // patch sweep) or long dense stages (many-body chain), three for the small articulated models (C3, C5: latency-bound, every extra
@@ -1318,11 +1320,76 @@ step_again:      // (a backward goto instead of a `for`: the instances without t
     ncon = 0;
     if (!post && !(M.disableflags & (MJH_DSBL_CONTACT | MJH_DSBL_CONSTRAINT))) {
       int conbase = 0;
+      // one (hfield, geom) pair, ip uniform: MuJoCo 2.3's prism decomposition.  The cells the other geom's bounding sphere
+      // covers (widened by the margin; any superset gives the same contacts), two triangles per cell, each a prism from its three
+      // elevations down to -base; lanes take prisms in chunks of 64 in prism order (row outer, column inner, triangle), each runs the
+      // portal algorithm against the geom (one contact at most), and a ballot / prefix compaction appends the contacts in prism order to
+      // the pair's staging until MJH_HFIELD_MAXCON.  Returns the pair's contact count.
+      auto hfield_pair = [&](const auto ipu) __attribute__((always_inline)) {     // (generic: only the HF instances instantiate it)
+        const Tab<int> geom_dataid{M.I, M.o_geom_dataid}, mesh_vertadr{M.I, M.o_mesh_vertadr}, mesh_vertnum{M.I, M.o_mesh_vertnum};
+        const DHField& H = C->H;
+        const int g1 = pair_geom1[ipu], g2 = pair_geom2[ipu], t2 = geom_type[g2];
+        float* const stp = s_stage + pair_stageadr[ipu] * RAW_STRIDE;
+        const int hid = geom_dataid[g1];
+        const int hnr = M.I[H.o_hfield_nrow + hid], hnc = M.I[H.o_hfield_ncol + hid];
+        const float* const hdat = M.F + H.o_hfield_data + M.I[H.o_hfield_adr + hid];
+        const float hsx = M.F[H.o_hfield_size + 4*hid], hsy = M.F[H.o_hfield_size + 4*hid + 1], hsz = M.F[H.o_hfield_size + 4*hid + 2], hsb = M.F[H.o_hfield_size + 4*hid + 3];
+        const float hmargin = fmaxf(geom_margin[g1], geom_margin[g2]);
+        CvxGeom P1, P2;
+        P1.type = MJH_GEOM_HFIELD; P1.vert = nullptr; P1.nvert = 0; P1.pad = P2.pad = 0;
+        P2.type = t2; P2.vert = nullptr; P2.nvert = 0;
+        if (t2 == MJH_GEOM_MESH) { const int id = geom_dataid[g2]; P2.vert = M.F + M.o_mesh_vert + 3 * mesh_vertadr[id]; P2.nvert = mesh_vertnum[id]; }
+        float lp[3];
+#pragma unroll
+        for (int k = 0; k < 9; k++) { P1.mat[k] = s_gmat[9*g1+k]; P2.mat[k] = s_gmat[9*g2+k]; }
+#pragma unroll
+        for (int k = 0; k < 3; k++) { P1.size[k] = 0; P2.pos[k] = s_gpos[3*g2+k]; P2.size[k] = s_p_gsize[3*g2+k]; lp[k] = P2.pos[k] - s_gpos[3*g1+k]; }
+        { float t[3]; rotvecT(t, P1.mat, lp); lp[0] = t[0]; lp[1] = t[1]; lp[2] = t[2]; }     // geom2's centre in the hfield frame
+        const float rb2 = s_p_rbound[g2], R = rb2 + hmargin;
+        const float dxc = 2.0f * hsx / (float)(hnc - 1), dyc = 2.0f * hsy / (float)(hnr - 1);
+        const bool outside = lp[0] + R < -hsx || lp[0] - R > hsx || lp[1] + R < -hsy || lp[1] - R > hsy || lp[2] - R > hsz || lp[2] + R < -hsb;
+        // (clamped as floats first: a non-finite pose gives an in-range cell, never an index outside the grid)
+        const int c0 = (int)fminf(fmaxf(floorf((lp[0] - R + hsx) / dxc), 0.0f), (float)(hnc - 2)), c1 = (int)fminf(fmaxf(floorf((lp[0] + R + hsx) / dxc), 0.0f), (float)(hnc - 2));
+        const int r0 = (int)fminf(fmaxf(floorf((lp[1] - R + hsy) / dyc), 0.0f), (float)(hnr - 2)), r1 = (int)fminf(fmaxf(floorf((lp[1] + R + hsy) / dyc), 0.0f), (float)(hnr - 2));
+        const int ncell = c1 - c0 + 1, nprism = outside ? 0 : 2 * ncell * (r1 - r0 + 1);
+        const float low = lp[2] - rb2 - hmargin;        // prisms whose three tops lie below this cannot touch geom2
+        int cnt = 0;
+        for (int base = 0; base < nprism && cnt < MJH_HFIELD_MAXCON; base += 64) {
+          const int k = min(base + lane, nprism - 1), cell = k >> 1, r = r0 + cell / ncell, c = c0 + cell % ncell;
+          // corners: (r, c), (r+1, c+1) — the diagonal — and (r, c+1) for the first triangle, (r+1, c) for the second
+          const int rc = (k & 1) ? r + 1 : r, cc = (k & 1) ? c : c + 1;
+          const float xa = -hsx + dxc * (float)c, xb = -hsx + dxc * (float)(c + 1), xc = -hsx + dxc * (float)cc;
+          const float ya = -hsy + dyc * (float)r, yb = -hsy + dyc * (float)(r + 1), yc = -hsy + dyc * (float)rc;
+          const float ta = hdat[r * hnc + c] * hsz, tb = hdat[(r + 1) * hnc + c + 1] * hsz, tcc = hdat[rc * hnc + cc] * hsz;
+          const bool act = base + lane < nprism && fmaxf(ta, fmaxf(tb, tcc)) >= low;
+          // the prism about the mean of its six vertices (the portal algorithm's interior point)
+          const float cx = (xa + xb + xc) * (1.0f / 3.0f), cy = (ya + yb + yc) * (1.0f / 3.0f), cz = (ta + tb + tcc - 3.0f * hsb) * (1.0f / 6.0f);
+          HfPrism hp;
+          hp.x[0] = xa - cx; hp.x[1] = xb - cx; hp.x[2] = xc - cx; hp.y[0] = ya - cy; hp.y[1] = yb - cy; hp.y[2] = yc - cy;
+          hp.top[0] = ta - cz; hp.top[1] = tb - cz; hp.top[2] = tcc - cz; hp.bot = -hsb - cz;
+          { const float cl[3] = {cx, cy, cz}; float cw[3]; rotvec(cw, P1.mat, cl);
+#pragma unroll
+            for (int q = 0; q < 3; q++) P1.pos[q] = s_gpos[3*g1+q] + cw[q]; }
+          float rbuf[RAW_STRIDE];
+#pragma unroll
+          for (int q = 0; q < RAW_STRIDE; q++) rbuf[q] = 0;
+          bool got = false;
+          if (wave_any(act)) got = c_convex_wave<true>(P1, P2, hmargin, rbuf, act, lane, &hp) != 0 && act;
+          const unsigned long long gm = __ballot(got);
+          const int idx = cnt + __popcll(gm & ((1ull << lane) - 1ull));
+          if (got && idx < MJH_HFIELD_MAXCON) {
+#pragma unroll
+            for (int q = 0; q < RAW_STRIDE; q++) stp[idx * RAW_STRIDE + q] = rbuf[q];
+          }
+          cnt += __popcll(gm);
+        }
+        return min(cnt, MJH_HFIELD_MAXCON);
+      };
       // one round: narrow phase of (up to) 64 candidate pairs, contacts appended in lane (= pair) order
       auto collide_round = [&](const int ip) __attribute__((always_inline)) {
         int n = 0, g1 = 0, g2 = 0; float margin = 0, gap = 0;
         float* st = s_stage;
-        CvxGeom G1, G2; bool cvx = false;
+        CvxGeom G1, G2; bool cvx = false, hf = false;
         G1.type = G2.type = 0; G1.vert = G2.vert = nullptr; G1.nvert = G2.nvert = 0; G1.pad = G2.pad = 0;
 #pragma unroll
         for (int k = 0; k < 9; k++) { G1.mat[k] = G2.mat[k] = 0; if (k < 3) { G1.pos[k] = G2.pos[k] = 0; G1.size[k] = G2.size[k] = 0; } }
@@ -1370,11 +1437,21 @@ step_again:      // (a backward goto instead of a `for`: the instances without t
               for (int k = 0; k < 3; k++) { G1.pos[k] = p1[k]; G2.pos[k] = p2[k]; G1.size[k] = z1[k]; G2.size[k] = z2[k]; }
 #pragma unroll
               for (int k = 0; k < 9; k++) { G1.mat[k] = m1[k]; G2.mat[k] = m2[k]; }
-            }
+            } else if (HF && t1 == MJH_GEOM_HFIELD) hf = true;
           }
         }
         // generic convex pairs (dev_convex.h): the lanes run the portal algorithm on their pairs, the wave serves their mesh scans
         if constexpr (EXTRA) { if (wave_any(cvx)) { const int nc = c_convex_wave(G1, G2, margin, st, cvx, lane); if (cvx) n = nc; } }
+        // height-field pairs: the wave serves them one after the other, lanes = prisms (hfield_pair)
+        if constexpr (HF) {
+          unsigned long long req = __ballot(hf);
+          while (req) {
+            const int owner = __ffsll((long long)req) - 1; req &= req - 1;
+            const int nh = hfield_pair(__builtin_amdgcn_readlane(ip, owner));
+            if (lane == owner) n = nh;
+          }
+          WSYNC();      // (the prism lanes wrote the pairs' staging; each owner lane reads its own below)
+        }
         const int incl = wave_incl_scan_i(n, lane);
         const int total = wave_last_i(incl);
         const int first = conbase + incl - n;

@@ -31,7 +31,7 @@ class Model:
 
     def __getattr__(self, name):
         c = self.__dict__.get("c")
-        if c is not None and name in capi._INT_SIZES + capi._INT_SIZES2 + ["meaninertia", "opt"]:
+        if c is not None and name in capi._INT_SIZES + capi._INT_SIZES2 + capi._INT_SIZES4 + ["meaninertia", "opt"]:
             return getattr(c, name)
         raise AttributeError(name)
 
