@@ -1,6 +1,7 @@
 """Build the C-ABI shared library (HIP kernels + host C++) in-tree for gfx950.
 
-One object per source under mujoco_sim_amd/build/ (re-made only when the source or one of its headers is newer), then one link:
+One object per source under mujoco_sim_amd/build/ (re-made only when the source, one of its headers or the flags changed), then one link
+(a library whose recorded link digest matches the present sources and flags is kept as it is, whether or not the objects still exist):
 the kernel translation unit (engine.hip, every mjh_step_kernel instance) takes about two minutes, the host files seconds."""
 import os
 import subprocess
@@ -64,6 +65,11 @@ def build(force=False, verbose=False):
         if force or not os.path.exists(op) or have != dg:
             stale.append(([hipcc] + sflags + ["-c", sp, "-o", op], stamp, dg))
         objs.append(op); digests.append(dg)
+    link_dg = _digest([], " ".join(digests))
+    link_stamp = os.path.join(OBJ, "libmjhip.sha256")
+    have = open(link_stamp).read().strip() if os.path.exists(link_stamp) else ""
+    if not force and os.path.exists(LIB) and have == link_dg:
+        return LIB      # the library was linked from exactly these sources and flags: the objects are intermediates and need not exist (a copy of the tree without them)
     # the stale units compile side by side (engine.hip and hfield.hip each take minutes); a few at a time
     from concurrent.futures import ThreadPoolExecutor
 
@@ -77,9 +83,6 @@ def build(force=False, verbose=False):
     with ThreadPoolExecutor(max_workers=max(1, min(4, len(stale)))) as pool:
         for r in [pool.submit(_compile, j) for j in stale]:
             r.result()
-    link_dg = _digest([], " ".join(digests))
-    link_stamp = os.path.join(OBJ, "libmjhip.sha256")
-    have = open(link_stamp).read().strip() if os.path.exists(link_stamp) else ""
     if force or not os.path.exists(LIB) or have != link_dg:
         # RCCL (mjh_group_*: the all-gather of the published state slice across the GPUs of a node) is resolved at run time
         # with dlopen, so the library loads on boxes without it

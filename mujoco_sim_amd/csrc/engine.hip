@@ -73,6 +73,7 @@ struct mjh_engine {
   // host-mapped staging area the device reads and writes directly — one small kernel per call instead of two or three pageable 2D
   // copies; the write side is a ring of slots, each fenced by an event, so mjh_set_cmd does not wait for the device
   float* h_io = nullptr; float* d_io = nullptr; hipEvent_t io_ev[MJH_IO_SLOTS] = {}; bool io_used[MJH_IO_SLOTS] = {}; unsigned io_next = 0;
+  int win_lean = -1;        // (tests, MJH_WINDOW_LEAN read at creation: 1 / 0 forces the lean / the fat window instance of a model within 256 rows; -1: by the rows seen)
   int* h_wn = nullptr; int* d_wn = nullptr; int cur_cohort = -1;   // window models: largest row count per cohort (host-mapped, written by mjh_order_kernel); cohort of the launch being issued
   int* h_dense = nullptr; int* d_dense = nullptr; hipEvent_t ev_dense[MJH_MAX_COHORTS][4] = {}; unsigned dense_epoch[MJH_MAX_COHORTS] = {}; bool dense_now[MJH_MAX_COHORTS];
   int* dI = nullptr; float* dF = nullptr; DConst* dC = nullptr;
@@ -151,6 +152,10 @@ static int window_tier(const mjh_engine* e) {
   const bool tier = sec32 ? seen > 32 * WN32_NW : seen + 16 > 16 * nwreg;
   // (models whose rows can exceed 256 — win_maxw > 16 — always get the tier: the 64-row section keeps the tiles of its last windows there,
   //  and which envs take that section is decided on the device)
+  // Without the tier the launcher takes the LEAN instance (window.hip: 376 registers — an assemble wavefront of another cohort fits on the same SIMD),
+  // with it the fat one (424).  Both sweep every env in the same form with the same values, so the lagged word above only picks where windows wait.
+  // (tests: MJH_WINDOW_LEAN = 1 / 0 forces the lean / the fat instance for models within 256 rows)
+  if (nl_env < 0 && e->win_lean >= 0 && e->M.win_maxw <= 16) return e->win_lean ? 0 : nl_full;
   return nl_env >= 0 ? nl_env : ((tier || e->M.win_maxw > 16) ? nl_full : 0);
 }
 // wmode (window chain of small free-body models): 0 the whole step; 1 the assemble launch only, every env handed over — the split API's
@@ -170,8 +175,8 @@ static int launch_on(mjh_engine* e, hipStream_t st, int env0, int n, int nsteps,
   const int nr = e->M.big ? 8 : (e->M.nv <= 16 ? 1 : (e->M.nv <= 32 ? 2 : 4));   // 8: many-body layout, running acceleration in LDS
   static const bool slim = !(getenv("MJH_WINDOW_SLIM") && atoi(getenv("MJH_WINDOW_SLIM")) == 0);
   if (window && slim) {
-    // the assemble-only instance (WPRE): the step kernel without any sweep of its own — 128 VGPRs instead of 236, so that its waves
-    // fit beside the window kernel's on a SIMD
+    // the assemble-only instance (WPRE): the step kernel without any sweep of its own — 116 - 119 VGPRs (allocated: 120) instead of 236, so that
+    // its waves fit beside the lean window kernel's on a SIMD (376 + 120 <= 512 registers: tests/test_window_register_budget.py)
     const bool cx = extra_instance(e->M) || e->S.xfrc_applied;
     static const bool slim_lds = !(getenv("MJH_WINDOW_SLIM_LDS") && atoi(getenv("MJH_WINDOW_SLIM_LDS")) == 0);
     static const int wpad = getenv("MJH_WPRE_LDS_PAD") ? std::max(0, atoi(getenv("MJH_WPRE_LDS_PAD"))) : 0;      // (occupancy experiments: bytes of unused LDS per assemble-only workgroup)
@@ -697,6 +702,7 @@ extern "C" int mjh_create(const mjh_model* m, int nenv, int device, void* stream
     if (((S.wstride / 64) & 1) == 0) S.wstride += 64;      // an odd number of 256-byte lines per env: the same offset of consecutive envs' slices does not fall on the same memory channel
     rc |= dev_alloc(e, &S.wbuf, (size_t)nenv * (size_t)S.wstride, true);
   }
+  if (const char* v = getenv("MJH_WINDOW_LEAN")) e->win_lean = atoi(v) != 0;
   if (M.window && e->lpt && nenv >= 1024) {
     HIPCHK(hipHostMalloc((void**)&e->h_wn, MJH_MAX_COHORTS * sizeof(int), hipHostMallocMapped));
     for (int g = 0; g < MJH_MAX_COHORTS; g++) e->h_wn[g] = 1 << 20;        // (nothing seen yet: keep the LDS tier)

@@ -384,8 +384,9 @@ DEV void wn_run32(const DConst* __restrict__ C, const DState& S, const int env0,
 // through ONE dot and ONE transpose-reduce per 64 rows: ~4.8 issue slots per row against 8 in the 16-row form (which serves four envs
 // with them: the wide form buys the shorter chain of the slowest envs with the SIMDs the window kernel leaves idle).  Every 16-lane row
 // of the wavefront carries the same a^ (lane q: dofs q and 16 + q / 2): the rows' partial J^T sums are exchanged by v_permlane16_swap /
-// v_permlane32_swap, the same sum in the same order in every lane.  WN64_NW windows (192 rows) register-resident, WN64_NT more (320 rows) with their tiles in LDS.  The form is a
-// function of the env's own row count (set by the assemble launch); same rows, same order, same row math and stopping rule as the
+// v_permlane32_swap, the same sum in the same order in every lane.  WN64_NW windows (192 rows) register-resident, WN64_NT more (320 rows) with their tiles in LDS
+// (the lean instance of launches without the LDS tier: two and one — 192 rows, what a model within 256 rows gives this form; an LDS window's
+// sweep is bitwise a register window's).  The form is a function of the model and the env's own row count (set by the assemble launch); same rows, same order, same row math and stopping rule as the
 // other forms, another grouping of the arithmetic (fp32 rounding).
 extern __shared__ __attribute__((aligned(16))) float wn_lds[];
 DEV float* wn_lds_base() { return wn_lds; }
@@ -509,7 +510,7 @@ DEV void wn_jt64(const float* J, const float x, float& a_lo, float& a_hi) {
 #define WN64_SWEEP(W, fw) WN64_SWEEP_X(W, fw, W.A, 0, 16, 32, 48, (void)0, (void)0, (void)0, (void)0)
 #endif
 
-DEV void wn_run64(const DConst* __restrict__ C, const DState& S, const int env0, const int nenv, const int xflags, const int blk, float* const lds64) {
+template <int N64W, int N64T> DEV void wn_run64(const DConst* __restrict__ C, const DState& S, const int env0, const int nenv, const int xflags, const int blk, float* const lds64) {
   const DModel& M = C->M;
   constexpr int NV = 24;
   const int lane = threadIdx.x, g = lane >> 4, q = lane & 15;
@@ -525,11 +526,11 @@ DEV void wn_run64(const DConst* __restrict__ C, const DState& S, const int env0,
   const bool lo_on = q < nv, hi_on = dhi < nv;
   const float as_lo = lo_on ? wb[WN_AS + q] : 0.0f, as_hi = hi_on ? wb[WN_AS + dhi] : 0.0f;
   const float ws_lo = lo_on ? wb[WN_AWS + q] : 0.0f, ws_hi = hi_on ? wb[WN_AWS + dhi] : 0.0f;
-  WnWin64 win[WN64_NW];
-  float f[WN64_NW];
+  WnWin64 win[N64W];
+  float f[N64W];
   const float* rows = wb + WN_ROWS + q;
 #pragma unroll
-  for (int w = 0; w < WN64_NW; w++) if (w < nwin) {
+  for (int w = 0; w < N64W; w++) if (w < nwin) {
     WnWin64& W = win[w];
     const bool ok = (4 * w + g) < nwin16;                      // (the assemble launch pads the last 16-row block with zero rows; a missing block is all zeros)
     wn_load_row<NV>(rows + (4 * w + g) * WN_NK * 16, ok, W.J, W.aref, W.R);
@@ -559,21 +560,21 @@ DEV void wn_run64(const DConst* __restrict__ C, const DState& S, const int env0,
       for (int sidx = 0; sidx < 16; sidx++) W.A[16 * G + sidx] = (16 * G + sidx) < lane ? ninv * acc[sidx] : 0.0f;
     }
   }
-  // the WN64_NT windows behind the register-resident ones (rows 193 .. 320): J^ and the constants in registers, their 64 x 64 tiles in LDS
+  // the N64T windows behind the register-resident ones (rows 193 .. 320; lean instance: 129 .. 192): J^ and the constants in registers, their 64 x 64 tiles in LDS
   // (16 KB each of the launch's LDS tier; [r / 4][lane][4]: the 16 entries of a lane row are four 16-byte reads), read again every sweep.
   // (All five windows in registers would take 500 of them — and a window kernel beyond 448 registers costs the 16-row form 10 % on S24,
   // measured: the forms share one kernel.)
   struct WnTail { float J[NV]; float aref, R, nw, half; };
-  WnTail TLS[WN64_NT];
-  float ftl[WN64_NT];
+  WnTail TLS[N64T > 0 ? N64T : 1];
+  float ftl[N64T > 0 ? N64T : 1];
   float* const tile = lds64 + lane * 4;
 #pragma unroll
-  for (int t = 0; t < WN64_NT; t++) {
+  for (int t = 0; t < N64T; t++) {
     ftl[t] = 0.0f;
-    if (WN64_NW + t < nwin) {
+    if (N64W + t < nwin) {
     WnTail& TL = TLS[t];
-    const bool ok = (4 * (WN64_NW + t) + g) < nwin16;
-    wn_load_row<NV>(rows + (4 * (WN64_NW + t) + g) * WN_NK * 16, ok, TL.J, TL.aref, TL.R);
+    const bool ok = (4 * (N64W + t) + g) < nwin16;
+    wn_load_row<NV>(rows + (4 * (N64W + t) + g) * WN_NK * 16, ok, TL.J, TL.aref, TL.R);
     float diag = 0.0f;
 #pragma unroll
     for (int k = 0; k < NV; k++) diag += TL.J[k] * TL.J[k];
@@ -608,12 +609,12 @@ DEV void wn_run64(const DConst* __restrict__ C, const DState& S, const int env0,
     const float4 t0_ = *(const float4*)(tp_), t1_ = *(const float4*)(tp_ + 256), t2_ = *(const float4*)(tp_ + 512), t3_ = *(const float4*)(tp_ + 768); \
     T[0] = t0_.x; T[1] = t0_.y; T[2] = t0_.z; T[3] = t0_.w; T[4] = t1_.x; T[5] = t1_.y; T[6] = t1_.z; T[7] = t1_.w; \
     T[8] = t2_.x; T[9] = t2_.y; T[10] = t2_.z; T[11] = t2_.w; T[12] = t3_.x; T[13] = t3_.y; T[14] = t3_.z; T[15] = t3_.w; } while (0)
-#define WN64_FOR_TAILS(...) do { _Pragma("unroll") for (int t = 0; t < WN64_NT; t++) if (WN64_NW + t < nwin) { WnTail& TL = TLS[t]; float& ft = ftl[t]; __VA_ARGS__ } } while (0)
+#define WN64_FOR_TAILS(...) do { _Pragma("unroll") for (int t = 0; t < N64T; t++) if (N64W + t < nwin) { WnTail& TL = TLS[t]; float& ft = ftl[t]; __VA_ARGS__ } } while (0)
   // ---- warm start
   float a_lo = as_lo, a_hi = as_hi;
 #pragma unroll
-  for (int w = 0; w < WN64_NW; w++) f[w] = 0.0f;
-#define WN64_FOR_WINDOWS(...) do { _Pragma("unroll") for (int w = 0; w < WN64_NW; w++) if (w < nwin) { WnWin64& W = win[w]; float& fw = f[w]; __VA_ARGS__ } } while (0)
+  for (int w = 0; w < N64W; w++) f[w] = 0.0f;
+#define WN64_FOR_WINDOWS(...) do { _Pragma("unroll") for (int w = 0; w < N64W; w++) if (w < nwin) { WnWin64& W = win[w]; float& fw = f[w]; __VA_ARGS__ } } while (0)
   if (!(M.disableflags & MJH_DSBL_WARMSTART)) {
     float da_lo = 0.0f, da_hi = 0.0f;
     WN64_FOR_WINDOWS({
@@ -639,9 +640,9 @@ DEV void wn_run64(const DConst* __restrict__ C, const DState& S, const int env0,
     cost = wn_rowsum_f(cost); wn_rows4_sum2(cost, dummy);
     if (cost > 0.0f) {
 #pragma unroll
-      for (int w = 0; w < WN64_NW; w++) f[w] = 0.0f;
+      for (int w = 0; w < N64W; w++) f[w] = 0.0f;
 #pragma unroll
-      for (int t = 0; t < WN64_NT; t++) ftl[t] = 0.0f;
+      for (int t = 0; t < N64T; t++) ftl[t] = 0.0f;
     } else { a_lo += da_lo; a_hi += da_hi; }
   }
   // ---- sweeps
@@ -718,7 +719,11 @@ template <int NV> DEV void wn_jt2(const float* JA, const float xa, const float* 
 // Only launches WITHOUT the LDS tier take it (instance XL; S24's default): beside the tier's 36 KB the 12 KB would cost the fourth window wavefront
 // of a CU its place (S24D: 5.83 -> 4.67 M, measured).
 #define WN_XLDS_BYTES(nvt, nw) (((nvt) == 24 && WN_FILL && WN_X_LDS) ? ((nw) / 2) * 4 * 64 * 16 : 0)
-template <int NV, int NW, bool XL = false>
+// N64W / N64T: 64-row windows of the 64-row section that are register-resident / that keep their tiles in LDS.  Launches with the LDS tier
+// (and every launch of a model whose rows can exceed 256) run <.., WN64_NW, WN64_NT>; launches without it — instance XL, models within 256 rows:
+// S24 — run the LEAN instance <.., WN64_NW_LEAN, WN64_NT_LEAN>: 376 registers instead of 424, so that an assemble wavefront (120) fits on the
+// same SIMD; its one LDS window (rows 129 .. 192) takes the place of the 16-row form's cross tiles.  Same forms, same values in both (window_pgs.h).
+template <int NV, int NW, bool XL = false, int N64W = WN64_NW, int N64T = WN64_NT>
 __global__ __launch_bounds__(64, 1) void mjh_window_kernel(const DConst* __restrict__ C, const DState S, const int env0, const int nenv, const int nl, const int xflags, const int n32waves, const int n64waves) {
   // the first n64waves wavefronts: the section of the envs with the most rows (one per wavefront, 64-row windows); the next n32waves: the
   // section of the envs with many rows (two per wavefront, 32-row windows); dispatched first — they are the launch's longest jobs
@@ -728,7 +733,7 @@ __global__ __launch_bounds__(64, 1) void mjh_window_kernel(const DConst* __restr
 #endif
   if constexpr (NV == 24) {
 #ifndef WN_NO_F64
-    if ((int)blockIdx.x < n64waves) { wn_run64(C, S, env0, nenv, xflags, (int)blockIdx.x, wn_lds_base()); return; }
+    if ((int)blockIdx.x < n64waves) { wn_run64<N64W, N64T>(C, S, env0, nenv, xflags, (int)blockIdx.x, wn_lds_base()); return; }
 #endif
     if ((int)blockIdx.x < n64waves + n32waves) { wn_run32(C, S, env0, nenv, xflags, (int)blockIdx.x - n64waves); return; }
   }

@@ -61,6 +61,17 @@
 #ifndef WN64_NT
 #define WN64_NT 2       // ... and the ones behind them whose tiles live in LDS (320 rows in all; they need the launch's LDS tier: 2 x 16 KB)
 #endif
+// Launches without the LDS tier (models whose rows stay within 256 — win_maxw <= 16, S24 — while no env of the cohort is beyond 128 rows) run a
+// LEAN instance of the window kernel, mjh_window_kernel<24, 6, true, WN64_NW_LEAN, WN64_NT_LEAN>: its 64-row section keeps two windows in registers
+// and the third one's tile in LDS (16 KB, in the place of the 16-row form's cross tiles, which a 64-row wavefront does not use).  Every register-
+// resident 64-row window is 92 registers: with two the kernel allocates 376 registers instead of 424, which leaves the 120 an assemble wavefront
+// needs on the same SIMD (376 + 120 <= 512).  The same envs take the same form in either instance (up to 64 WN64_NW rows, set by the assemble
+// launch), and an LDS window's sweep is bitwise a register window's: results do not depend on the instance.
+#ifndef WN64_NW_LEAN
+#define WN64_NW_LEAN 2
+#endif
+#define WN64_NT_LEAN (WN64_NW - WN64_NW_LEAN)
+#define WN64_TILE_BYTES (64 * 64 * 4)       // LDS tile of one 64-row window
 
 // Assemble launch (mjh_step_kernel with PH_PRE, free-body instance): the constraint blocks of this env -> window rows in global memory.
 // blki / blkf / J: the block tables in LDS (step_kernel.h); sinv = M^-1/2 per dof.  Returns the number of rows (0: too many, not written).
