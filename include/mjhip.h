@@ -428,6 +428,36 @@ int mjh_destroy_objects(mjh_engine*, int n, const int* env, const int* body);
 /* initial pose / twist of a spawned free body (mj_ros.cpp:1406-1412) */
 int mjh_set_body_pose(mjh_engine*, int env, int body, const double pos[3], const double quat[4], const double vel[6]);
 
+/* Batched ray casting: mj_ray for every environment (the reference's robots carry laser scanners: the hsrb4s base scanner, PR2's
+ * tilt laser mount; MuJoCo answers such queries with mj_ray and the rangefinder sensor).  nray rays against the geoms of envs
+ * [env0, env0+n) at the envs' present qpos.  dist is the smallest x >= 0 for which pnt + x vec lies on the surface of a visible
+ * geom — in units of |vec|, vec is not normalised for the caller —, geomid that geom; a miss is dist = -1, geomid = -1.
+ *   plane: front (+z) face only, bounded by size[0] / size[1] where those are > 0;
+ *   sphere, capsule, ellipsoid, cylinder (flat caps), box: nearest non-negative root (an origin inside hits the far surface);
+ *   height field: the solid the collision code uses (two triangles per cell sharing the diagonal (r,c)-(r+1,c+1), side walls and
+ *     base down to -size[3]), hit at its nearest surface from any side;
+ *   mesh geoms (and hfield geoms without an asset) are invisible: mjh_ray_skipped_geoms counts them.
+ * A geom of a body whose spawn / destroy slot is inactive in an env is invisible there; geom sizes are the env's own where per-env
+ * sizes are set (mjh_set_env_param).  Call-sequence rules are those of mjh_get_geom_state (a pending mjh_step1 is issued first and a
+ * window hand-over is dropped); nothing of the envs' state, statistics or time is written. */
+typedef struct mjh_ray_options {
+  int site;         /* >= 0: pnt / vec are given in this site's frame and follow it per env; -1: world frame */
+  int bodyexclude;  /* geoms of this body are invisible (mj_ray's bodyexclude); -1: none */
+  int flg_static;   /* 0: geoms of static bodies (body_weldid 0) are invisible; 1: visible */
+  int per_env;      /* 0: one ray set [nray] shared by all envs; 1: pnt / vec are [n][nray] */
+  double cutoff;    /* > 0: hits with dist beyond it are misses (rangefinder cutoff); <= 0: none */
+} mjh_ray_options;
+void mjh_ray_default_options(mjh_ray_options*);   /* -1, -1, 1, 0, 0 */
+/* host pointers, doubles: converts, calls the device form and synchronises.  options may be NULL (the defaults).  A zero vec, nray <= 0,
+ * an env range, site or body id out of range return MJH_ERR_ARG and launch nothing. */
+int mjh_ray(mjh_engine*, int env0, int n, int nray, const double* pnt, const double* vec,
+            const mjh_ray_options*, double* dist /*[n][nray]*/, int* geomid /*[n][nray]*/);
+/* device pointers, fp32: enqueued on the engine's stream, returns without synchronising; the results are valid after
+ * mjh_synchronize (a zero vec cannot be refused here: such a ray misses) */
+int mjh_ray_device(mjh_engine*, int env0, int n, int nray, const float* d_pnt, const float* d_vec,
+                   const mjh_ray_options*, float* d_dist, int* d_geomid);
+int mjh_ray_skipped_geoms(const mjh_model*);     /* geoms no ray can see (mesh geoms, hfield geoms without an asset) */
+
 /* zero-copy export for the single ROS state topic: packs time(1)+qpos(nq)+qvel(nv)
  * fp32 per env into a caller-provided DEVICE buffer [nenv*(1+nq+nv)] on the engine's
  * stream (feeds the RCCL all-gather). */

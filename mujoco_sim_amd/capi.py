@@ -115,6 +115,10 @@ class LoadOptions(C.Structure):
                 ("odom_joints", C.c_uint), ("nrobot_pose", C.c_int), ("robot_pose_body", C.POINTER(C.c_char_p)), ("robot_pose", c_double_p), ("parent_child_exclude", C.c_int)]
 
 
+class RayOptions(C.Structure):
+    _fields_ = [("site", C.c_int), ("bodyexclude", C.c_int), ("flg_static", C.c_int), ("per_env", C.c_int), ("cutoff", C.c_double)]
+
+
 # every symbol include/mjhip.h declares: (name, restype, argtypes)
 _vp = C.c_void_p
 SYMBOLS = [
@@ -204,6 +208,10 @@ SYMBOLS = [
     ("mjh_set_body_pose", C.c_int, [_vp, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p]),
     ("mjh_spawn_objects", C.c_int, [_vp, C.c_int, c_int_p, c_int_p, c_double_p, c_double_p, c_double_p]),
     ("mjh_destroy_objects", C.c_int, [_vp, C.c_int, c_int_p, c_int_p]),
+    ("mjh_ray_default_options", None, [C.POINTER(RayOptions)]),
+    ("mjh_ray", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, C.POINTER(RayOptions), c_double_p, c_int_p]),
+    ("mjh_ray_device", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.POINTER(RayOptions), _vp, _vp]),
+    ("mjh_ray_skipped_geoms", C.c_int, [Model_p]),
     ("mjh_export_state_device", C.c_int, [_vp, _vp]),
     ("mjh_state_stride", C.c_int, [_vp]),
     ("mjh_mirror_create", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(_vp)]),

@@ -15,6 +15,7 @@
 
 #include "../../include/mjhip.h"
 #include "step_kernel.h"
+#include "dev_ray.h"
 
 void mjh_set_error(const std::string& s);  // model_builder.cpp
 hipError_t mjh_launch_window(hipStream_t st, int nvt, int grid, size_t lds, const DConst* dC, const DState& S, int env0, int n, int nl, int wxf, int n32, int n64);   // window.hip
@@ -108,6 +109,9 @@ struct mjh_engine {
   bool step1_pending = false;   // mjh_step1 has been called, its launch is deferred to the next entry point (fused with mjh_inverse if that is the one)
   // in-engine joint-space PD effort controller (mjh_set_pd_controller): ddq written on the device in front of every step
   float pd_kp = 0, pd_kd = 0; float* pd_target = nullptr; bool pd_on = false;
+  // ray casting (mjh_ray / mjh_ray_device, ray.hip): per-geom and per-hfield tables uploaded at the first call, staging of the host form
+  int4* ray_ginfo = nullptr; RayHField* ray_hf = nullptr; float* ray_hfdata = nullptr; bool ray_ready = false;
+  float* ray_io = nullptr; size_t ray_io_floats = 0;
 };
 
 static int pad32(int n) { return ((n + 31) / 32) * 32; }
@@ -764,6 +768,7 @@ extern "C" void mjh_destroy(mjh_engine* e) {
   for (auto& p : e->tev) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
   for (void* p : e->allocs) (void)hipFree(p);
   if (e->scratch) (void)hipFree(e->scratch);
+  if (e->ray_io) (void)hipFree(e->ray_io);
   if (e->h_dense) (void)hipHostFree(e->h_dense);
   if (e->h_wn) (void)hipHostFree(e->h_wn);
   if (e->h_io) (void)hipHostFree(e->h_io);
@@ -1806,6 +1811,132 @@ extern "C" int mjh_debug_stop_at(mjh_engine* e, int stage, int with_inverse) {
   ENG(e);
   if (stage < 1 || stage > 14) { mjh_set_error("mjh_debug_stop_at: stage must be 1..14"); return MJH_ERR_ARG; }
   return launch(e, 0, e->nenv, 1, PH_STEP1 | PH_STEP2 | (with_inverse ? PH_INV : 0), stage << 8);
+}
+
+// ---- batched ray casting (mj_ray for every env: laser scans, range finders, terrain height under a foot).  The launch chain is the
+// position-stage launch of the env range (PH_FKONLY with XF_GEOM, plus XF_BODY for rays given in a site's frame) into the engine's
+// export scratch, exactly as fk_export issues it, then mjh_ray_kernel (ray.hip) on the same stream.  Nothing of the envs' state,
+// statistics or time is written.
+// what a ray can see of geom g: its type, or -1 (mesh geoms: the model keeps no faces; an hfield geom without an asset)
+static int ray_geom_type(const mjh_model* m, int g) {
+  const int t = m->geom_type[g];
+  if (t == MJH_GEOM_MESH) return -1;
+  if (t == MJH_GEOM_HFIELD && !(m->nhfield > 0 && m->geom_dataid && m->geom_dataid[g] >= 0 && m->geom_dataid[g] < m->nhfield)) return -1;
+  return t < MJH_GEOM_PLANE || t > MJH_GEOM_BOX ? -1 : t;
+}
+extern "C" int mjh_ray_skipped_geoms(const mjh_model* m) {
+  if (!m) return 0;
+  int n = 0;
+  for (int g = 0; g < m->ngeom; g++) n += ray_geom_type(m, g) < 0;
+  return n;
+}
+extern "C" void mjh_ray_default_options(mjh_ray_options* o) {
+  if (!o) return;
+  o->site = -1; o->bodyexclude = -1; o->flg_static = 1; o->per_env = 0; o->cutoff = 0.0;
+}
+static int ray_tables(mjh_engine* e) {
+  if (e->ray_ready) return MJH_OK;
+  const mjh_model* m = e->model;
+  std::vector<int4> gi((size_t)std::max(m->ngeom, 1));
+  for (int g = 0; g < m->ngeom; g++) {
+    const int t = ray_geom_type(m, g), b = m->geom_bodyid[g];
+    gi[g] = make_int4(t, b, m->body_weldid[b] == 0 ? 1 : 0, t == MJH_GEOM_HFIELD ? m->geom_dataid[g] : -1);
+  }
+  int rc = dev_alloc(e, &e->ray_ginfo, gi.size(), false);
+  if (rc) return rc;
+  HIPCHK(hipMemcpy(e->ray_ginfo, gi.data(), gi.size() * sizeof(int4), hipMemcpyHostToDevice));
+  if (m->nhfield > 0) {
+    std::vector<RayHField> hf((size_t)m->nhfield);
+    std::vector<float> hd((size_t)std::max(m->nhfielddata, 1));
+    for (int h = 0; h < m->nhfield; h++) {
+      hf[h].nrow = m->hfield_nrow[h]; hf[h].ncol = m->hfield_ncol[h]; hf[h].adr = m->hfield_adr[h]; hf[h].pad = 0;
+      for (int k = 0; k < 4; k++) hf[h].size[k] = (float)m->hfield_size[4*h + k];
+    }
+    for (int i = 0; i < m->nhfielddata; i++) hd[i] = (float)m->hfield_data[i];
+    rc = dev_alloc(e, &e->ray_hf, hf.size(), false);
+    if (!rc) rc = dev_alloc(e, &e->ray_hfdata, hd.size(), false);
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(e->ray_hf, hf.data(), hf.size() * sizeof(RayHField), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(e->ray_hfdata, hd.data(), hd.size() * sizeof(float), hipMemcpyHostToDevice));
+  }
+  e->ray_ready = true;
+  return MJH_OK;
+}
+// argument checks shared by both entry points: nothing is launched when one fails
+static int ray_check(const mjh_engine* e, int env0, int n, int nray, const void* pnt, const void* vec, const mjh_ray_options* o, const void* dist, const void* geomid) {
+  if (env0 < 0 || n <= 0 || env0 + n > e->nenv) { mjh_set_error("mjh_ray: env range out of bounds"); return MJH_ERR_ARG; }
+  if (nray <= 0 || (long long)nray * n > 0x3fffffffLL) { mjh_set_error("mjh_ray: nray must be positive (and n * nray below 2^30)"); return MJH_ERR_ARG; }
+  if (!pnt || !vec || !dist || !geomid) { mjh_set_error("mjh_ray: null pointer"); return MJH_ERR_ARG; }
+  if (o) {
+    if (o->site < -1 || o->site >= e->model->nsite) { mjh_set_error("mjh_ray: site id out of range"); return MJH_ERR_ARG; }
+    if (o->bodyexclude < -1 || o->bodyexclude >= e->model->nbody) { mjh_set_error("mjh_ray: bodyexclude out of range"); return MJH_ERR_ARG; }
+  }
+  return MJH_OK;
+}
+extern "C" int mjh_ray_device(mjh_engine* e, int env0, int n, int nray, const float* d_pnt, const float* d_vec, const mjh_ray_options* opt,
+                              float* d_dist, int* d_geomid) {
+  ENG(e);
+  int rc = ray_check(e, env0, n, nray, d_pnt, d_vec, opt, d_dist, d_geomid);
+  if (!rc) rc = ray_tables(e);
+  if (rc) return rc;
+  mjh_ray_options o; mjh_ray_default_options(&o);
+  if (opt) o = *opt;
+  const mjh_model* m = e->model;
+  const int ng = e->M.ngeom, nb = e->M.nbody;
+  const size_t fg = (size_t)n * 3 * ng, fm = (size_t)n * 9 * ng, fx = o.site >= 0 ? (size_t)n * 3 * nb : 0, fq = o.site >= 0 ? (size_t)n * 4 * nb : 0;
+  rc = ensure_scratch(e, fg + fm + fx + fq);
+  if (rc) return rc;
+  RayArgs A{};
+  A.gpos = e->scratch; A.gmat = e->scratch + fg; A.xpos = e->scratch + fg + fm; A.xquat = e->scratch + fg + fm + fx;
+  {
+    StateGuard guard(&e->S);
+    e->S.x_gpos = e->scratch; e->S.x_gmat = e->scratch + fg;
+    if (o.site >= 0) { e->S.x_xpos = e->scratch + fg + fm; e->S.x_xquat = e->scratch + fg + fm + fx; }
+    rc = launch(e, env0, n, 1, PH_FKONLY, XF_GEOM | (o.site >= 0 ? XF_BODY : 0));
+  }
+  if (rc) return rc;
+  if (e->S.p_geom_size) { A.size = e->S.p_geom_size; A.size_stride = e->S.p_stride; } else { A.size = e->dF + e->M.o_geom_size; A.size_stride = 0; }
+  A.slot_mask = e->S.slot_mask; A.sbase = nb > 32 ? nb - 32 : 0;
+  A.ginfo = e->ray_ginfo; A.hf = e->ray_hf; A.hf_data = e->ray_hfdata;
+  A.pnt = d_pnt; A.vec = d_vec; A.dist = d_dist; A.geomid = d_geomid;
+  A.env0 = env0; A.n = n; A.nray = nray; A.ngeom = ng; A.nbody = nb;
+  A.per_env = o.per_env ? 1 : 0; A.bodyexclude = o.bodyexclude; A.flg_static = o.flg_static ? 1 : 0; A.cutoff = o.cutoff > 0 ? (float)o.cutoff : 0.0f;
+  A.site_body = -1;
+  if (o.site >= 0) {
+    A.site_body = m->site_bodyid[o.site];
+    for (int k = 0; k < 3; k++) A.site_pos[k] = (float)m->site_pos[3 * o.site + k];
+    for (int k = 0; k < 4; k++) A.site_quat[k] = (float)m->site_quat[4 * o.site + k];
+  }
+  HIPCHK(mjh_launch_ray(e->stream, A));
+  return MJH_OK;
+}
+extern "C" int mjh_ray(mjh_engine* e, int env0, int n, int nray, const double* pnt, const double* vec, const mjh_ray_options* opt,
+                       double* dist, int* geomid) {
+  ENG(e);
+  int rc = ray_check(e, env0, n, nray, pnt, vec, opt, dist, geomid);
+  if (rc) return rc;
+  const size_t nin = (size_t)(opt && opt->per_env ? n : 1) * nray, nout = (size_t)n * nray;
+  std::vector<float> h(6 * nin);
+  for (size_t i = 0; i < nin; i++) {
+    if (vec[3*i] == 0.0 && vec[3*i+1] == 0.0 && vec[3*i+2] == 0.0) { mjh_set_error("mjh_ray: zero direction vector"); return MJH_ERR_ARG; }
+    for (int k = 0; k < 3; k++) { h[3*i + k] = (float)pnt[3*i + k]; h[3*nin + 3*i + k] = (float)vec[3*i + k]; }
+  }
+  const size_t need = 6 * nin + 2 * nout;
+  if (need > e->ray_io_floats) {
+    if (e->ray_io) { HIPCHK(hipStreamSynchronize(e->stream)); HIPCHK(hipFree(e->ray_io)); e->ray_io = nullptr; e->ray_io_floats = 0; }
+    HIPCHK(hipMalloc((void**)&e->ray_io, need * sizeof(float)));
+    e->ray_io_floats = need;
+  }
+  float* const d_in = e->ray_io; float* const d_dist = e->ray_io + 6 * nin; int* const d_gid = (int*)(e->ray_io + 6 * nin + nout);
+  HIPCHK(hipMemcpyAsync(d_in, h.data(), 6 * nin * sizeof(float), hipMemcpyHostToDevice, e->stream));
+  rc = mjh_ray_device(e, env0, n, nray, d_in, d_in + 3 * nin, opt, d_dist, d_gid);
+  if (rc) { (void)hipStreamSynchronize(e->stream); return rc; }      // (the upload reads `h`)
+  std::vector<float> hd(nout);
+  HIPCHK(hipMemcpyAsync(hd.data(), d_dist, nout * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(geomid, d_gid, nout * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  for (size_t i = 0; i < nout; i++) dist[i] = (double)hd[i];
+  return MJH_OK;
 }
 
 extern "C" int mjh_nenv(const mjh_engine* e) { return e ? e->nenv : 0; }

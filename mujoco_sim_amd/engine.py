@@ -41,6 +41,10 @@ class Model:
     def name2id(self, objtype, name):
         return self.lib.mjh_name2id(self.ptr, objtype, name.encode())
 
+    def ray_skipped_geoms(self):
+        """geoms no ray can see: mesh geoms and hfield geoms without an asset (mjh_ray_skipped_geoms)"""
+        return self.lib.mjh_ray_skipped_geoms(self.ptr)
+
     def replicate(self, copies):
         """sub-wave packing: `copies` instances of the moving bodies in one model (mjh_model_replicate)"""
         return Model(self.lib.mjh_model_replicate(self.ptr, int(copies)), self.lib)
@@ -303,6 +307,40 @@ class Engine:
     def set_body_pose(self, env, body, pos, quat=None, vel=None):
         a = [None if x is None else np.ascontiguousarray(x, dtype=np.float64) for x in (pos, quat, vel)]
         _chk(self.lib, self.lib.mjh_set_body_pose(self.h, env, body, *[capi.dptr(x) for x in a]), "mjh_set_body_pose")
+
+    # ---- ray casting (mj_ray for every env)
+    def _ray_options(self, per_env, options):
+        o = capi.RayOptions()
+        self.lib.mjh_ray_default_options(C.byref(o))
+        o.per_env = int(per_env)
+        for k, v in options.items():
+            if k not in ("site", "bodyexclude", "flg_static", "cutoff"):
+                raise TypeError(f"unknown ray option {k!r}")
+            setattr(o, k, v)
+        return o
+
+    def ray(self, pnt, vec, env0=0, n=None, **options):
+        """rays pnt + x vec against the geoms of envs [env0, env0 + n): [nray, 3] arrays are one ray set shared by all envs, [n, nray, 3]
+        arrays one set per env.  options: site, bodyexclude, flg_static, cutoff (mjh_ray_options).
+        -> (dist [n, nray] float64 in units of |vec|, geomid [n, nray] int32); a miss is (-1, -1)"""
+        n = self.nenv - env0 if n is None else n
+        p = np.ascontiguousarray(pnt, dtype=np.float64); v = np.ascontiguousarray(vec, dtype=np.float64)
+        per_env = p.ndim == 3
+        if p.shape != v.shape or p.shape[-1] != 3 or (per_env and p.shape[0] != n):
+            raise ValueError("pnt / vec must both be [nray, 3] or [n, nray, 3]")
+        nray = p.shape[-2] if p.ndim >= 2 else 1
+        o = self._ray_options(per_env, options)
+        dist = np.zeros((n, nray)); gid = np.zeros((n, nray), dtype=np.int32)
+        _chk(self.lib, self.lib.mjh_ray(self.h, env0, n, nray, capi.dptr(p), capi.dptr(v), C.byref(o), capi.dptr(dist), capi.iptr(gid)), "mjh_ray")
+        return dist, gid
+
+    def ray_device(self, d_pnt, d_vec, d_dist, d_geomid, nray, env0=0, n=None, per_env=False, **options):
+        """mjh_ray_device: device addresses (data_ptr()) of fp32 pnt / vec [nray, 3] (per_env: [n, nray, 3]), fp32 dist and int32 geomid
+        [n, nray]; enqueued on the engine's stream, valid after synchronize()"""
+        n = self.nenv - env0 if n is None else n
+        o = self._ray_options(per_env, options)
+        _chk(self.lib, self.lib.mjh_ray_device(self.h, env0, n, int(nray), C.c_void_p(d_pnt), C.c_void_p(d_vec), C.byref(o),
+                                               C.c_void_p(d_dist), C.c_void_p(d_geomid)), "mjh_ray_device")
 
     def export_state_device(self, device_ptr):
         _chk(self.lib, self.lib.mjh_export_state_device(self.h, C.c_void_p(device_ptr)), "mjh_export_state_device")

@@ -1,0 +1,412 @@
+"""Batched ray casting on the device (mjh_ray / mjh_ray_device) against the fp64 reference of ray_ref.py.
+
+The reference is always fed the device's own geom poses (mjh_get_geom_state), so only the ray arithmetic is under test.  On
+robust rays (ray_ref.robust) the geom ids are equal and |dist - ref| <= 5e-5 max(1, dist): scene coordinates of at most 5 m give an
+fp32 ulp near 5e-7, robustness bounds the conditioning at 10, i.e. about 5e-6; the tolerance is ten times that.  The share of
+non-robust rays, measured with the device poses, stays within 10 %."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import mujoco_sim_amd as ms
+import ray_ref as rr
+from helpers import D, set_opt
+from mujoco_sim_amd import capi
+from mujoco_sim_amd.engine import MjhError
+
+pytestmark = pytest.mark.gpu
+
+TOL = 5e-5
+MJH_ERR_ARG = -1
+
+
+def _check(name, dist, gid, scene, rays, cutoff=0.0):
+    """dist / gid of ONE env against the reference on the robust rays; returns the largest scaled error"""
+    ref_d, ref_g = rr.cast(rays[0], rays[1], scene, cutoff=cutoff)
+    rob = rr.robust(rays, scene)
+    share = 1.0 - rob.mean()
+    hit = rob & (ref_g >= 0)
+    err = np.abs(dist - ref_d) / np.maximum(1.0, np.abs(ref_d))
+    worst = float(err[hit].max()) if hit.any() else 0.0
+    print(f"{name}: {len(rob)} rays, non-robust share {share:.3f}, hits {int(hit.sum())}, max scaled error {worst:.3e}")
+    assert share <= 0.10, name
+    assert (gid[rob] == ref_g[rob]).all(), name
+    assert (dist[rob & (ref_g < 0)] == -1.0).all(), name
+    assert worst <= TOL, name
+    return worst
+
+
+def _build(lib, spec, gravity=(0, 0, 0)):
+    """model from a ray_ref spec: static geoms on the world body, every free one on a free body of its own"""
+    b = lib.mjh_builder_create()
+    set_opt(lib, b, timestep=0.002, gravity=list(gravity))
+    k = 0
+    for g in spec:
+        if g["free"]:
+            bd = lib.mjh_builder_add_body(b, b"free%d" % k, 0, D(*g["pos"]), D(*g["quat"]), 0.0)
+            lib.mjh_builder_add_joint(b, None, bd, 0, None, None, None, 0, 0, 0, 0, 0)
+            assert lib.mjh_builder_add_geom(b, b"g%d" % k, bd, g["type"], D(*g["size"]), None, None, None, -1, -1, -1, -1) >= 0
+        else:
+            assert lib.mjh_builder_add_geom(b, b"g%d" % k, 0, g["type"], D(*g["size"]), D(*g["pos"]), D(*g["quat"]), None, -1, -1, -1, -1) >= 0
+        k += 1
+    m = ms.Model(lib.mjh_builder_compile(b), lib)
+    lib.mjh_builder_destroy(b)
+    return m
+
+
+def _device_scene(e, m, env, size=None, visible=None, hfield=None):
+    gp, gm = e.get_geom_state(env, 1)
+    return rr.scene_from_device(gp[0], gm[0], m.array("geom_size") if size is None else size, m.array("geom_type"), visible, hfield)
+
+
+# ------------------------------------------------------------------ 1. every primitive type, static and free, tile edges
+@pytest.fixture(scope="module")
+def prim(lib):
+    spec = rr.primitives_spec()
+    m = _build(lib, spec)
+    e = ms.Engine(m, 4)
+    scene = _device_scene(e, m, 0)
+    yield m, e, scene, spec
+    e.close()
+
+
+@pytest.mark.parametrize("nray", [1, 63, 65, 130])
+def test_primitives_world_frame(prim, nray):
+    m, e, scene, _ = prim
+    P, V = rr.primitive_rays(scene, 130)
+    rays = (P[:nray], V[:nray])
+    dist, gid = e.ray(*rays)
+    assert dist.shape == (4, nray)
+    for env in range(4):      # no per-env data: every env sees the same scene
+        _check(f"primitives nray {nray} env {env}", dist[env], gid[env], scene, rays)
+    hit_types = set(int(scene["type"][g]) for g in gid[0] if g >= 0)
+    if nray == 130:
+        assert hit_types >= {rr.PLANE, rr.SPHERE, rr.CAPSULE, rr.ELLIPSOID, rr.CYLINDER, rr.BOX}
+        body = m.array("geom_bodyid")
+        assert {bool(body[g]) for g in gid[0] if g >= 0} == {False, True}, "static and free geoms are hit"
+
+
+def test_primitives_directed_cases(prim):
+    m, e, scene, spec = prim
+    types = scene["type"]
+    sph = int(np.nonzero(types == rr.SPHERE)[0][0]); box = int(np.nonzero(types == rr.BOX)[0][-1])
+    P = np.array([scene["pos"][sph], scene["pos"][sph] + [0.05, 0.02, -0.03], scene["pos"][box], scene["pos"][box] + [0.04, -0.03, 0.02],
+                  [2.8, -1.8, -0.5], [3.5, 0.0, 1.0], [2.9, -1.9, 1.0]])
+    V = np.array([[0.3, -0.2, 0.9], [1.0, 0, 0], [0.2, 0.5, -0.4], [0, 0, 1.5], [0, 0, 1.0], [0, 0, -1.0], [0, 0, -0.5]])
+    dist, gid = e.ray(P, V, n=1)
+    _check("directed", dist[0], gid[0], scene, (P, V))
+    assert gid[0, 0] == sph and gid[0, 1] == sph and gid[0, 2] == box and gid[0, 3] == box      # origins inside: the far surface
+    assert dist[0, 0] == pytest.approx(0.22 / np.linalg.norm(V[0]), abs=1e-5)
+    assert gid[0, 4] == -1 and dist[0, 4] == -1.0       # plane back face
+    assert gid[0, 5] == -1                               # beyond the bounded plane's edge
+    assert gid[0, 6] == 0 and dist[0, 6] == pytest.approx(2.0, abs=1e-5)      # just inside the edge, in units of |vec| = 0.5
+
+
+# ------------------------------------------------------------------ 2. height field, 3 x 5
+def test_hfield(lib):
+    b = lib.mjh_builder_create()
+    el = (C.c_double * rr.HF_ELEV.size)(*rr.HF_ELEV.ravel())
+    h = lib.mjh_builder_add_hfield(b, b"terrain", rr.HF_NROW, rr.HF_NCOL, D(*rr.HF_SIZE), el)
+    assert h >= 0
+    assert lib.mjh_builder_add_hfield_geom(b, b"ground", 0, h, D(*rr.HF_POS), D(*rr.HF_QUAT), None, -1, -1, -1) >= 0
+    bd = lib.mjh_builder_add_body(b, b"far", 0, D(0, 0, 50.0), None, 0.0)      # (a model needs a moving body; it is out of every ray's way)
+    lib.mjh_builder_add_joint(b, None, bd, 0, None, None, None, 0, 0, 0, 0, 0)
+    lib.mjh_builder_add_geom(b, b"fg", bd, rr.SPHERE, D(0.05, 0, 0), None, None, None, -1, -1, -1, -1)
+    set_opt(lib, b, gravity=[0, 0, 0])
+    m = ms.Model(lib.mjh_builder_compile(b), lib)
+    lib.mjh_builder_destroy(b)
+    assert m.ray_skipped_geoms() == 0
+    e = ms.Engine(m, 4)
+    import hfield_ref
+    hf = hfield_ref.hfield_of(m, 0)
+    assert np.allclose(hf[3], rr.HF_ELEV)
+    scene = _device_scene(e, m, 0, hfield={0: hf})
+    rays = rr.hfield_rays(rr.hfield_scene())
+    dist, gid = e.ray(*rays)
+    for env in range(4):
+        _check(f"hfield env {env}", dist[env], gid[env], scene, rays)
+    # the directed cases themselves are robust and hit what they are meant to
+    nd = 12
+    rob = rr.robust(rays, scene)
+    assert rob[:nd].all()
+    assert (gid[0, :nd] == [0, 0, 0, 0, 0, 0, 0, 0, 0, -1, 0, 0]).all()
+    e.close()
+
+
+# ------------------------------------------------------------------ 3. S24, per-env sizes, env0 = 3, n = 5, after 20 steps
+def test_s24_per_env_sizes_by_env_id(lib):
+    m = ms.scene("s24")
+    e = ms.Engine(m, 16)
+    tab = e.load_s24()
+    e.step(20)
+    env0, n = 3, 5
+    scenes = [_device_scene(e, m, env0 + i, size=tab["geom_size"][env0 + i]) for i in range(n)]
+    rays = rr.s24_rays(scenes[0], 96)
+    dist, gid = e.ray(*rays, env0=env0, n=n)
+    for i in range(n):
+        _check(f"s24 env {env0 + i}", dist[i], gid[i], scenes[i], rays)
+    assert not np.array_equal(dist[0], dist[1]), "per-env sizes and poses: the scans differ"
+    # an env's scan under another env's sizes is a different scan: the sizes used are the env's own
+    other, _ = rr.cast(rays[0], rays[1], dict(scenes[0], size=np.asarray(tab["geom_size"][env0 + 1]).reshape(-1, 3)))
+    own, _ = rr.cast(rays[0], rays[1], scenes[0])
+    assert np.abs(other - own).max() > 1e-3
+    e.close()
+
+
+# ------------------------------------------------------------------ 4. site frame on moving bodies, per-env rays
+def _site_rays(rng, n, nray):
+    P = rng.uniform(-0.02, 0.02, size=(n, nray, 3))
+    V = rng.normal(size=(n, nray, 3)); V /= np.linalg.norm(V, axis=2, keepdims=True)
+    return P, V * rng.uniform(0.5, 2.0, size=(n, nray, 1))
+
+
+def _check_site(name, e, m, site, site_body, spos, squat, nsteps, rng, nray=200):
+    n = e.nenv
+    e.step(nsteps)
+    P, V = _site_rays(rng, n, nray)
+    dist, gid = e.ray(P, V, site=site, bodyexclude=site_body)
+    xp, xq = e.get_body_state()
+    Rs = rr.quat2mat(squat).reshape(3, 3)
+    Pw = np.zeros_like(P); Vw = np.zeros_like(V)
+    for i in range(n):
+        Rb = rr.quat2mat(xq[i, site_body]).reshape(3, 3)
+        Pw[i] = xp[i, site_body] + (Rb @ np.asarray(spos)) + P[i] @ (Rb @ Rs).T
+        Vw[i] = V[i] @ (Rb @ Rs).T
+    dw, gw = e.ray(Pw, Vw, bodyexclude=site_body)
+    vis = m.array("geom_bodyid") != site_body
+    for i in range(n):
+        scene = _device_scene(e, m, i, visible=vis)
+        _check(f"{name} env {i} (site frame)", dist[i], gid[i], scene, (Pw[i], Vw[i]))
+        rob = rr.robust((Pw[i], Vw[i]), scene)
+        assert (gid[i][rob] == gw[i][rob]).all()
+        assert np.abs(dist[i] - dw[i])[rob].max() <= TOL * max(1.0, dist[i].max())
+    assert not np.allclose(xp[0, site_body], xp[1, site_body]), "the bodies have moved apart: the site follows each env's own"
+
+
+def test_site_on_free_box(lib):
+    b = lib.mjh_builder_create()
+    set_opt(lib, b, timestep=0.005)
+    # (a bounded floor: from 1.5 m up, a beam within a few degrees of the horizon would meet an unbounded one tens of metres away, at a
+    #  grazing angle no 1e-4 shift leaves alone; 200 beams per env keep the share of such rays a stable figure)
+    lib.mjh_builder_add_geom(b, b"floor", 0, rr.PLANE, D(3.0, 3.0, 0.05), None, None, None, -1, -1, -1, -1)
+    lib.mjh_builder_add_geom(b, b"pillar", 0, rr.CYLINDER, D(0.2, 0.8, 0), D(1.2, 0.3, 0.8), None, None, -1, -1, -1, -1)
+    lib.mjh_builder_add_geom(b, b"block", 0, rr.BOX, D(0.3, 0.4, 0.5), D(-1.0, -0.8, 0.5), D(0.9239, 0, 0, 0.3827), None, -1, -1, -1, -1)
+    bd = lib.mjh_builder_add_body(b, b"box", 0, D(0, 0, 1.5), None, 0.0)
+    lib.mjh_builder_add_joint(b, None, bd, 0, None, None, None, 0, 0, 0, 0, 0)
+    lib.mjh_builder_add_geom(b, b"boxg", bd, rr.BOX, D(0.1, 0.08, 0.06), None, None, None, -1, -1, -1, -1)
+    spos, squat = (0.12, 0.0, 0.02), tuple(np.array([0.8, 0.2, -0.3, 0.4]) / np.linalg.norm([0.8, 0.2, -0.3, 0.4]))
+    site = lib.mjh_builder_add_site(b, b"laser", bd, D(*spos), D(*squat))
+    assert site >= 0
+    m = ms.Model(lib.mjh_builder_compile(b), lib)
+    lib.mjh_builder_destroy(b)
+    n = 6
+    e = ms.Engine(m, n)
+    rng = np.random.default_rng(7)
+    q = np.tile(m.array("qpos0"), (n, 1)); v = np.zeros((n, m.nv))
+    for i in range(n):
+        q[i, 3:7] = rr.random_quat(rng); v[i] = rng.normal(size=6) * [0.5, 0.5, 0.5, 2, 2, 2]
+    e.set_state(qpos=q, qvel=v)
+    _check_site("free box", e, m, site, bd, spos, squat, 10, rng)
+    e.close()
+
+
+def test_site_on_arm7_tip(lib):
+    """mjh_scene_arm7 has no site and a compiled model takes none: the same chain is built again from the scene's own tables, with a
+    site on the last link"""
+    a = ms.scene("arm7", 0)
+    bp, bq = a.array("body_pos").reshape(-1, 3), a.array("body_quat").reshape(-1, 4)
+    gs, gpos, gq = a.array("geom_size").reshape(-1, 3), a.array("geom_pos").reshape(-1, 3), a.array("geom_quat").reshape(-1, 4)
+    jr, ja, par, gb = a.array("jnt_range").reshape(-1, 2), a.array("jnt_axis").reshape(-1, 3), a.array("body_parentid"), a.array("geom_bodyid")
+    b = lib.mjh_builder_create()
+    set_opt(lib, b, timestep=0.005)
+    for g in range(a.ngeom):
+        if gb[g] == 0:
+            lib.mjh_builder_add_geom(b, b"w%d" % g, 0, int(a.array("geom_type")[g]), D(*gs[g]), D(*gpos[g]), D(*gq[g]), None, -1, -1, -1, -1)
+    lib.mjh_builder_add_geom(b, b"post", 0, rr.CAPSULE, D(0.1, 0.6, 0), D(1.0, 0.4, 0.7), None, None, -1, 0, 0, -1)
+    lib.mjh_builder_add_geom(b, b"crate", 0, rr.BOX, D(0.3, 0.3, 0.3), D(0.2, -1.0, 0.3), None, None, -1, 0, 0, -1)
+    ids = {0: 0}
+    for k in range(1, a.nbody):
+        ids[k] = lib.mjh_builder_add_body(b, b"link%d" % k, ids[int(par[k])], D(*bp[k]), D(*bq[k]), 0.0)
+        j = int(a.array("body_jntadr")[k])
+        lib.mjh_builder_add_joint(b, b"j%d" % k, ids[k], 3, None, D(*ja[j]), D(*jr[j]), 0, 0, 0, 0, 0)
+    for g in range(a.ngeom):
+        if gb[g] > 0:
+            lib.mjh_builder_add_geom(b, b"lg%d" % g, ids[int(gb[g])], int(a.array("geom_type")[g]), D(*gs[g]), D(*gpos[g]), D(*gq[g]), None, -1, 0, 0, -1)
+    tip = ids[a.nbody - 1]
+    spos, squat = (0.0, 0.0, 0.12), (0.7071067811865476, 0.0, 0.7071067811865476, 0.0)
+    site = lib.mjh_builder_add_site(b, b"tip", tip, D(*spos), D(*squat))
+    assert site >= 0
+    m = ms.Model(lib.mjh_builder_compile(b), lib)
+    lib.mjh_builder_destroy(b)
+    assert m.nv == 7
+    n = 5
+    e = ms.Engine(m, n)
+    rng = np.random.default_rng(9)
+    q = np.tile(m.array("qpos0"), (n, 1)) + rng.uniform(-0.4, 0.4, size=(n, 7))
+    q[:, 3] = -1.5 + rng.uniform(-0.3, 0.3, size=n); q[:, 5] = 1.0 + rng.uniform(-0.3, 0.3, size=n)      # (inside their ranges)
+    e.set_state(qpos=q, qvel=rng.normal(size=(n, 7)))
+    _check_site("arm7 tip", e, m, site, tip, spos, squat, 10, rng)
+    e.close()
+
+
+# ------------------------------------------------------------------ 5. options
+def test_options_bodyexclude_static_cutoff(prim, lib):
+    m, e, scene, _ = prim
+    rays = rr.primitive_rays(scene, 130)
+    body = m.array("geom_bodyid")
+    d0, g0 = e.ray(*rays, n=1)
+    hits = g0[0][g0[0] >= 0]
+    bx = int(body[hits[body[hits] > 0][0]])        # a free body some ray hits
+    d1, g1 = e.ray(*rays, n=1, bodyexclude=bx)
+    _check("bodyexclude", d1[0], g1[0], dict(scene, visible=body != bx), rays)
+    was = (g0[0] >= 0) & (body[np.maximum(g0[0], 0)] == bx)
+    assert was.any() and not (body[g1[0][g1[0] >= 0]] == bx).any()
+    assert np.array_equal(d1[0][~was], d0[0][~was]) and np.array_equal(g1[0][~was], g0[0][~was]), "exactly that body's geoms are hidden"
+    d2, g2 = e.ray(*rays, n=1, flg_static=0)
+    _check("flg_static 0", d2[0], g2[0], dict(scene, visible=body != 0), rays)
+    assert (body[g2[0][g2[0] >= 0]] != 0).all() and (body[g0[0][g0[0] >= 0]] == 0).any()
+    # S24: floor and walls are static
+    s = ms.scene("s24"); es = ms.Engine(s, 4); es.load_s24()
+    sc = _device_scene(es, s, 0)
+    rs = rr.s24_rays(sc, 96)
+    _, gs_all = es.ray(*rs, n=1); _, gs_dyn = es.ray(*rs, n=1, flg_static=0)
+    sb = s.array("geom_bodyid")
+    assert (sb[gs_all[0][gs_all[0] >= 0]] == 0).any() and (sb[gs_dyn[0][gs_dyn[0] >= 0]] > 0).all()
+    es.close()
+    # cutoff: a hit at 1.2
+    P, V = np.array([[2.8, -1.8, 1.2]]), np.array([[0, 0, -1.0]])
+    for cut, want in ((0.0, (1.2, 0)), (1.0, (-1.0, -1)), (1.5, (1.2, 0))):
+        d, g = e.ray(P, V, n=1, cutoff=cut)
+        assert d[0, 0] == pytest.approx(want[0], abs=1e-5) and g[0, 0] == want[1], cut
+
+
+# ------------------------------------------------------------------ 6. slots
+def test_inactive_slot_is_invisible_in_that_env_only(prim):
+    m, e, scene, _ = prim
+    body = m.array("geom_bodyid")
+    g = int(np.nonzero((scene["type"] == rr.BOX) & (body > 0))[0][0]); bd = int(body[g])
+    P = np.array([scene["pos"][g] + [0, 0, 1.0]]); V = np.array([[0, 0, -1.0]])
+    d0, g0 = e.ray(P, V)
+    assert (g0[:, 0] == g).all()
+    e.set_slot_active(bd, 0, env0=2, n=1)
+    try:
+        d1, g1 = e.ray(P, V)
+        assert g1[2, 0] != g and d1[2, 0] != d0[2, 0]
+        assert np.array_equal(np.delete(g1, 2, axis=0), np.delete(g0, 2, axis=0)) and np.array_equal(np.delete(d1, 2, axis=0), np.delete(d0, 2, axis=0))
+        rd, rg = rr.cast(P, V, dict(scene, visible=body != bd))
+        assert g1[2, 0] == rg[0] and d1[2, 0] == pytest.approx(rd[0], abs=TOL * max(1, rd[0]))
+    finally:
+        e.set_slot_active(bd, 1, env0=2, n=1)
+    d2, g2 = e.ray(P, V)
+    assert np.array_equal(g2, g0) and np.array_equal(d2, d0)
+
+
+# ------------------------------------------------------------------ 7. more geoms than one staging pass holds
+def test_more_geoms_than_one_staging_pass(lib):
+    spec = rr.many_spheres_spec()
+    assert len(spec) > 64
+    b = lib.mjh_builder_create()
+    set_opt(lib, b, gravity=[0, 0, 0])
+    for k, g in enumerate(spec):
+        lib.mjh_builder_add_geom(b, b"g%d" % k, 0, g["type"], D(*g["size"]), D(*g["pos"]), D(*g["quat"]), None, -1, 0, 0, -1)
+    bd = lib.mjh_builder_add_body(b, b"far", 0, D(0, 0, 50.0), None, 0.0)
+    lib.mjh_builder_add_joint(b, None, bd, 0, None, None, None, 0, 0, 0, 0, 0)
+    lib.mjh_builder_add_geom(b, b"fg", bd, rr.SPHERE, D(0.05, 0, 0), None, None, None, -1, 0, 0, -1)
+    m = ms.Model(lib.mjh_builder_compile(b), lib)
+    lib.mjh_builder_destroy(b)
+    e = ms.Engine(m, 4)
+    scene = _device_scene(e, m, 0)
+    rays = rr.many_spheres_rays(scene)
+    dist, gid = e.ray(*rays)
+    for env in range(4):
+        _check(f"many spheres env {env}", dist[env], gid[env], scene, rays)
+    assert (gid[0] >= 64).any() and ((gid[0] >= 0) & (gid[0] < 64)).any(), "geoms of both staging passes are hit"
+    e.close()
+
+
+# ------------------------------------------------------------------ 8. mesh geoms are skipped, not hit
+def test_mesh_geoms_are_skipped(lib):
+    m = rr.mesh_model(lib)
+    assert m.ray_skipped_geoms() == 2
+    e = ms.Engine(m, 4)
+    types = m.array("geom_type")
+    gp, _ = e.get_geom_state(0, 1)
+    mesh = np.nonzero(types == rr.MESH)[0]
+    P = np.array([gp[0, mesh[0]] + [0, 0, 1.0], gp[0, mesh[1]] + [0, 0, 1.0], gp[0, mesh[0]] + [-1.0, 0, 0]])
+    V = np.array([[0, 0, -1.0], [0, 0, -1.0], [1.0, 0, 0]])
+    dist, gid = e.ray(P, V)      # succeeds: never MJH_ERR_UNSUPPORTED
+    scene = _device_scene(e, m, 0)
+    _check("mesh model", dist[0], gid[0], scene, (P, V))
+    assert not np.isin(gid, mesh).any()
+    ball = int(np.nonzero(types == rr.SPHERE)[0][0])
+    assert gid[0, 0] == ball and gid[0, 1] == 0 and gid[0, 2] == -1      # through the first mesh onto the ball, through the second onto the floor
+    e.close()
+
+
+# ------------------------------------------------------------------ 9. the device entry point; nothing of the state is written
+def _snapshot(e):
+    t, q, v, w = e.get_state()
+    return [t, q, v, w, e.get_stats(), e.get_field("qacc"), e.get_field("qfrc_applied")]
+
+
+def test_ray_device_same_bits_and_read_only(lib):
+    import torch
+    m = ms.scene("s24")
+    a, b = ms.Engine(m, 16), ms.Engine(m, 16)
+    tab = a.load_s24(); b.load_s24()
+    a.step(7); b.step(7)
+    sc = _device_scene(a, m, 3, size=tab["geom_size"][3])
+    P, V = rr.s24_rays(sc, 96)
+    before = _snapshot(a)
+    env0, n = 3, 5
+    dist, gid = a.ray(P, V, env0=env0, n=n)
+    dev = torch.device("cuda:0")
+    tp = torch.tensor(P, dtype=torch.float32, device=dev).contiguous(); tv = torch.tensor(V, dtype=torch.float32, device=dev).contiguous()
+    td = torch.full((n, 96), 7.0, dtype=torch.float32, device=dev); tg = torch.full((n, 96), 7, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    a.ray_device(tp.data_ptr(), tv.data_ptr(), td.data_ptr(), tg.data_ptr(), 96, env0=env0, n=n)
+    a.synchronize()
+    assert np.array_equal(td.cpu().numpy().view(np.uint32), dist.astype(np.float32).view(np.uint32))
+    assert np.array_equal(tg.cpu().numpy(), gid)
+    assert np.array_equal(dist.astype(np.float32).astype(np.float64), dist), "mjh_ray returns the device's fp32 results"
+    after = _snapshot(a)
+    for x, y in zip(before, after):
+        assert np.array_equal(x, y)
+    a.step(3); b.step(3)
+    for x, y in zip(_snapshot(a), _snapshot(b)):
+        assert np.array_equal(x, y), "a step after a ray call equals a step without one"
+    # ... and between the halves of a split step
+    a.step1(); a.ray(P, V, env0=env0, n=n); a.step2()
+    b.step1(); b.get_geom_state(env0, n); b.step2()
+    for x, y in zip(_snapshot(a), _snapshot(b)):
+        assert np.array_equal(x, y), "the call sequence rules are those of mjh_get_geom_state"
+    a.close(); b.close()
+
+
+# ------------------------------------------------------------------ 10. errors
+def test_errors_launch_nothing(prim, lib):
+    m, e, scene, _ = prim
+    P, V = rr.primitive_rays(scene, 8)
+    good_d, good_g = e.ray(P, V)
+    dist = np.full((4, 8), 7.0); gid = np.full((4, 8), 7, dtype=np.int32)
+    o = capi.RayOptions(); lib.mjh_ray_default_options(C.byref(o))
+
+    def call(env0=0, n=4, nray=8, pnt=P, vec=V, **kw):
+        oo = capi.RayOptions(); lib.mjh_ray_default_options(C.byref(oo))
+        for k, v in kw.items():
+            setattr(oo, k, v)
+        p = np.ascontiguousarray(pnt, float); v = np.ascontiguousarray(vec, float)
+        return lib.mjh_ray(e.h, env0, n, nray, capi.dptr(p), capi.dptr(v), C.byref(oo), capi.dptr(dist), capi.iptr(gid))
+
+    Vz = V.copy(); Vz[5] = 0.0
+    assert call(vec=Vz) == MJH_ERR_ARG
+    assert call(nray=0) == MJH_ERR_ARG and call(nray=-3) == MJH_ERR_ARG
+    assert call(env0=2, n=3) == MJH_ERR_ARG and call(env0=-1, n=2) == MJH_ERR_ARG and call(env0=4, n=1) == MJH_ERR_ARG
+    assert call(site=0) == MJH_ERR_ARG and call(site=-2) == MJH_ERR_ARG            # the model has no site
+    assert call(bodyexclude=m.nbody) == MJH_ERR_ARG and call(bodyexclude=-2) == MJH_ERR_ARG
+    assert (dist == 7.0).all() and (gid == 7).all(), "nothing was launched: the outputs are untouched"
+    with pytest.raises(MjhError):
+        e.ray(P, Vz)
+    assert call() == 0
+    assert np.array_equal(dist, good_d) and np.array_equal(gid, good_g)
