@@ -131,6 +131,7 @@ RDEV float ray_box(const float* p, const float* v, const float* s) {
 // (r,c) (r+1,c+1) (r,c+1) and (r,c) (r+1,c+1) (r+1,c), down to z = -size[3] — hit at its nearest surface from any side: the top
 // triangles (two-sided: an origin inside the solid leaves through them), the four side walls below the terrain and the base.
 // The ray is clipped to the field's box first; only the cells under the clipped segment are visited, column strip by column strip.
+// A ray never passes between two cells: see the tolerance of the walk in ray_hfield.
 RDEV float ray_hfield_height(const RayHField& H, const float* __restrict__ hd, float x, float y) {
   const float dx = 2.0f * H.size[0] / (float)(H.ncol - 1), dy = 2.0f * H.size[1] / (float)(H.nrow - 1);
   const float fx = fminf(fmaxf((x + H.size[0]) / dx, 0.0f), (float)(H.ncol - 1)), fy = fminf(fmaxf((y + H.size[1]) / dy, 0.0f), (float)(H.nrow - 1));
@@ -168,29 +169,37 @@ RDEV float ray_hfield(const float* p, const float* v, const RayHField& H, const 
       }
     }
   }
-  // top triangles of the cells under the segment [t0, t1]
+  // top triangles of the cells under the segment [t0, t1].  Everything that places the ray on the grid comes from ONE pair of
+  // expressions, the grid coordinates gu + x ud (column line c where it equals c) and gw + x wd (row line r): the strips and rows to
+  // visit and a cell's u, w in [0, 1] alike, so a ray on a grid line is never rounded one way when the cell is chosen and the other
+  // way when the triangle is tested.  The rounding of a grid coordinate grows with its size — half an ulp of the index per operation,
+  // 4e-6 at index 33 — so the tolerance does too: 4 ulps of the largest operand (|gu| + ncol: the origin may be far outside).  Within
+  // it of a line the neighbouring strip / row is visited as well and a triangle takes the point; the terrain is continuous, so the
+  // neighbour's plane that far past its edge is off by the tolerance times a height difference of the cell, below fp32 resolution
+  // of the distance.
   const int nc = H.ncol, nr = H.nrow;
   const float dx = 2.0f * sx / (float)(nc - 1), dy = 2.0f * sy / (float)(nr - 1);
-  const float xa = p[0] + t0 * v[0], xb = p[0] + t1 * v[0];
-  const int c0 = (int)fminf(fmaxf(floorf((fminf(xa, xb) + sx) / dx), 0.0f), (float)(nc - 2));
-  const int c1 = (int)fminf(fmaxf(floorf((fmaxf(xa, xb) + sx) / dx), 0.0f), (float)(nc - 2));
-  const float eps = 1e-6f;
+  const float gu = (p[0] + sx) / dx, gw = (p[1] + sy) / dy, ud = v[0] / dx, wd = v[1] / dy;
+  const float tolu = 4.8e-7f * (fabsf(gu) + (float)nc), tolw = 4.8e-7f * (fabsf(gw) + (float)nr);
+  const float ua = gu + t0 * ud, ub = gu + t1 * ud;
+  const int c0 = (int)fminf(fmaxf(floorf(fminf(ua, ub) - tolu), 0.0f), (float)(nc - 2));
+  const int c1 = (int)fminf(fmaxf(floorf(fmaxf(ua, ub) + tolu), 0.0f), (float)(nc - 2));
+  // (a strip taken tolu wider moves the ends of the segment over it by tolu |wd / ud| rows)
+  const float rtol = v[0] != 0.0f ? tolw + tolu * fabsf(wd / ud) : tolw;
   for (int c = c0; c <= c1; c++) {
     // the part [ta, tb] of the segment over this strip of columns (all of it when the ray runs along the strip)
     float ta = t0, tb = t1;
-    const float xc = -sx + dx * (float)c;
     if (v[0] != 0.0f) {
-      const float a = (xc - p[0]) / v[0], b = (xc + dx - p[0]) / v[0];
+      const float a = ((float)c - gu) / ud, b = ((float)(c + 1) - gu) / ud;
       ta = fmaxf(ta, fminf(a, b)); tb = fminf(tb, fmaxf(a, b));
     }
-    if (ta > tb) ta = tb = 0.5f * (ta + tb);      // (rounding at the segment's ends: c0 / c1 come from the same end points)
-    const float ya = p[1] + ta * v[1], yb = p[1] + tb * v[1];
-    const int r0 = (int)fminf(fmaxf(floorf((fminf(ya, yb) + sy) / dy - eps), 0.0f), (float)(nr - 2));
-    const int r1 = (int)fminf(fmaxf(floorf((fmaxf(ya, yb) + sy) / dy + eps), 0.0f), (float)(nr - 2));
+    if (ta > tb) ta = tb = 0.5f * (ta + tb);      // (a strip the segment only touches within the tolerance)
+    const float wa = gw + ta * wd, wb = gw + tb * wd;
+    const int r0 = (int)fminf(fmaxf(floorf(fminf(wa, wb) - rtol), 0.0f), (float)(nr - 2));
+    const int r1 = (int)fminf(fmaxf(floorf(fmaxf(wa, wb) + rtol), 0.0f), (float)(nr - 2));
     for (int r = r0; r <= r1; r++) {
-      const float yr = -sy + dy * (float)r;
       const float z00 = hd[r * nc + c] * sz, z01 = hd[r * nc + c + 1] * sz, z10 = hd[(r + 1) * nc + c] * sz, z11 = hd[(r + 1) * nc + c + 1] * sz;
-      const float u0 = (p[0] - xc) / dx, w0 = (p[1] - yr) / dy, ud = v[0] / dx, wd = v[1] / dy;    // cell coordinates u, w in [0, 1] along the ray
+      const float u0 = gu - (float)c, w0 = gw - (float)r;      // cell coordinates of the origin
 #pragma unroll
       for (int k = 0; k < 2; k++) {
         // z = z00 + u A + w B over the triangle: first u >= w, second w >= u
@@ -198,8 +207,8 @@ RDEV float ray_hfield(const float* p, const float* v, const RayHField& H, const 
         const float den = v[2] - ud * A - wd * B;
         if (den == 0.0f) continue;
         const float x = (z00 + u0 * A + w0 * B - p[2]) / den;
-        const float u = u0 + x * ud, w = w0 + x * wd;
-        const bool in = k ? (w >= u - eps && u >= -eps && w <= 1.0f + eps) : (u >= w - eps && w >= -eps && u <= 1.0f + eps);
+        const float u = (gu + x * ud) - (float)c, w = (gw + x * wd) - (float)r;
+        const bool in = k ? (w >= u - (tolu + tolw) && u >= -tolu && w <= 1.0f + tolw) : (u >= w - (tolu + tolw) && w >= -tolw && u <= 1.0f + tolu);
         if (in) best = ray_pick(best, x);
       }
     }

@@ -7,7 +7,8 @@ pnt + x vec on the surface of a visible geom (in units of |vec|) and that geom; 
 Geoms: a plane is hit on its front (+z) face only and bounded by size[0], size[1] where those are > 0; sphere, capsule,
 ellipsoid, cylinder (flat caps) and box at the nearest non-negative root (an origin inside hits the far surface); a height
 field is the solid the collision code uses — two triangles per cell sharing the diagonal (r, c)-(r+1, c+1), side walls and base
-down to -size[3] — hit at its nearest surface from any side; meshes are invisible.
+down to -size[3] — hit at its nearest surface from any side (a triangle includes its edges with an absolute slack of 1e-12 in its
+barycentric coordinates, so a ray that lies on a grid line cannot fall between two neighbours); meshes are invisible.
 
 robust() marks the rays whose result does not flip under a 1e-4 shift of the origin: grazing and edge rays change geom or
 jump in distance on fp32 rounding, and no tolerance on the device result is meaningful for them.
@@ -117,6 +118,9 @@ def hfield_height(hf, x, y):
     return np.where(u >= w, z00 + u * (z01 - z00) + w * (z11 - z01), z00 + w * (z10 - z00) + u * (z11 - z10))
 
 
+EDGE_SLACK = 1e-12
+
+
 def _hfield(P, V, hf):
     nrow, ncol, size, data = hf
     sx, sy, sz, sb = size
@@ -154,7 +158,9 @@ def _hfield(P, V, hf):
                     q1, q2 = Q @ e1, Q @ e2
                     det = d11 * d22 - d12 * d12
                     b1, b2 = (d22 * q1 - d12 * q2) / det, (d11 * q2 - d12 * q1) / det
-                    best = _pick(best, x, (b1 >= 0) & (b2 >= 0) & (b1 + b2 <= 1))
+                    # (absolute slack: a ray exactly on an edge may miss both neighbours by one fp64 rounding; the terrain is
+                    #  continuous, so taking the neighbour's plane at its edge changes no distance)
+                    best = _pick(best, x, (b1 >= -EDGE_SLACK) & (b2 >= -EDGE_SLACK) & (b1 + b2 <= 1 + EDGE_SLACK))
     return best
 
 
@@ -380,6 +386,263 @@ def hfield_rays(scene, seed=5, nrand=100):
     P = np.array([t + R @ np.array(p) for p, _ in loc]); V = np.array([R @ np.array(v) for _, v in loc])
     Pr, Vr = make_rays(seed, scene, nrand, (-2.5, -2.5, -1.5), (2.5, 2.5, 2.5))
     return np.vstack([P, Pr]), np.vstack([V, Vr])
+
+
+# the terrains of the grid-line tests: cell indices up to 38 along y (A), along x (B), and a mid-sized grid (C)
+TERRAINS = {"A": (40, 9, (1.5, 6.0, 1.0, 0.1), 61), "B": (9, 40, (6.0, 1.5, 1.0, 0.1), 62), "C": (17, 33, (4.0, 2.0, 0.6, 0.3), 63)}
+
+
+def rolling(nrow, ncol, seed):
+    """elevation [nrow, ncol] in [0, 1] with min 0 and max 1, exact in float32: rolling ground (two waves) under uniform noise"""
+    rng = np.random.default_rng(seed)
+    r, c = np.meshgrid(np.arange(nrow), np.arange(ncol), indexing="ij")
+    e = np.sin(0.9 * r + rng.uniform(0, 6)) * np.cos(0.7 * c + rng.uniform(0, 6)) + 0.5 * np.sin(0.37 * (r + c) + rng.uniform(0, 6))
+    e = e + rng.uniform(-0.4, 0.4, size=e.shape)
+    e = (e - e.min()) / (e.max() - e.min())
+    e = e.astype(np.float32).astype(float)
+    e[e == e.max()] = 1.0; e[e == e.min()] = 0.0
+    return e
+
+
+def terrain(name):
+    """hf tuple (nrow, ncol, size[4], elevation [nrow, ncol]) of terrain A, B or C (fixed seed)"""
+    nrow, ncol, size, seed = TERRAINS[name]
+    return nrow, ncol, np.array(size, float), rolling(nrow, ncol, seed)
+
+
+def terrain_scene(hf):
+    """the field alone, unrotated at the world origin: the world frame is the geom's"""
+    return dict(pos=np.zeros((1, 3)), mat=np.eye(3).reshape(1, 9), size=np.zeros((1, 3)), type=np.array([HFIELD]), visible=np.ones(1, bool),
+                hfield={0: hf})
+
+
+def f32(*arrays):
+    """rounded to float32 (kept as float64 arrays): the ray the device sees is the ray the reference sees"""
+    out = tuple(np.asarray(a, float).astype(np.float32).astype(float) for a in arrays)
+    return out if len(out) > 1 else out[0]
+
+
+def grid_lines(hf):
+    """x of every column line, y of every row line (fp64, as the reference places them)"""
+    nrow, ncol, size, _ = hf
+    return -size[0] + 2 * size[0] * np.arange(ncol) / (ncol - 1), -size[1] + 2 * size[1] * np.arange(nrow) / (nrow - 1)
+
+
+def hfield_node_rays(hf):
+    """straight down at every interior grid node: (P, V, (r, c) of each ray)"""
+    nrow, ncol, size, _ = hf
+    xs, ys = grid_lines(hf)
+    rc = np.array([(r, c) for r in range(1, nrow - 1) for c in range(1, ncol - 1)])
+    k = np.arange(len(rc))
+    P = np.stack([xs[rc[:, 1]], ys[rc[:, 0]], size[2] + 0.25 + 0.05 * (k % 7)], axis=1)
+    V = np.stack([0 * k, 0 * k, -0.5 - 0.25 * (k % 3)], axis=1).astype(float)
+    return f32(P, V) + (rc,)
+
+
+def hfield_line_rays(hf, axis, seed, nray=600):
+    """rays in the vertical plane of an interior grid line: axis 1: a row line (vec.y == 0), axis 0: a column line (vec.x == 0); from
+    beside and above the field onto a point of the line at terrain height"""
+    nrow, ncol, size, _ = hf
+    rng = np.random.default_rng(seed)
+    lines = grid_lines(hf)[axis]
+    o = 1 - axis
+    P = np.zeros((nray, 3)); T = np.zeros((nray, 3))
+    P[:, axis] = T[:, axis] = lines[rng.integers(1, len(lines) - 1, size=nray)]
+    P[:, o] = rng.uniform(-size[o] - 1.0, size[o] + 1.0, size=nray); P[:, 2] = rng.uniform(size[2] + 0.2, size[2] + 1.5, size=nray)
+    T[:, o] = rng.uniform(-size[o], size[o], size=nray); T[:, 2] = rng.uniform(0, size[2], size=nray)
+    V = T - P
+    V *= (rng.uniform(0.5, 2.0, size=nray) / np.linalg.norm(V, axis=1))[:, None]
+    V[:, axis] = 0.0
+    return f32(P, V)
+
+
+def hfield_diagonal_rays(hf, seed, nray=400):
+    """along the cells' diagonals through grid nodes: vec = +-(dx, dy, -z), the origin a whole number of cells up the diagonal from
+    an interior node"""
+    nrow, ncol, size, _ = hf
+    rng = np.random.default_rng(seed)
+    xs, ys = grid_lines(hf)
+    dx, dy = xs[1] - xs[0], ys[1] - ys[0]
+    r, c = rng.integers(1, nrow - 1, size=nray), rng.integers(1, ncol - 1, size=nray)
+    k = rng.integers(1, 6, size=nray) * rng.choice([-1.0, 1.0], size=nray)       # cells back along the diagonal (either sense)
+    zc = rng.uniform(0.15, 0.6, size=nray) * size[2]                             # descent per cell
+    zn = rng.uniform(0.0, size[2], size=nray)                                    # the ray's height over the node
+    P = np.stack([xs[c] - k * dx, ys[r] - k * dy, zn + np.abs(k) * zc], axis=1)
+    V = np.stack([np.sign(k) * dx, np.sign(k) * dy, -zc], axis=1)
+    return f32(P, V)
+
+
+def hfield_grazing_rays(hf, seed, nray=400):
+    """low rays started inside the field's box above the surface: a slope of at most 0.15 either way"""
+    nrow, ncol, size, _ = hf
+    rng = np.random.default_rng(seed)
+    P = np.zeros((0, 3))
+    while len(P) < nray:
+        X = rng.uniform((-size[0], -size[1], 0.0), (size[0], size[1], size[2]), size=(4 * nray, 3))
+        P = np.vstack([P, X[X[:, 2] > hfield_height(hf, X[:, 0], X[:, 1]) + 0.02]])
+    P = P[:nray]
+    a = rng.uniform(0, 2 * np.pi, size=nray)
+    V = np.stack([np.cos(a), np.sin(a), rng.uniform(-0.15, 0.15, size=nray)], axis=1) * rng.uniform(0.5, 2.0, size=(nray, 1))
+    return f32(P, V)
+
+
+def hfield_random_rays(hf, seed, nray=400):
+    size = hf[2]
+    m = max(size[0], size[1]) + 1.0
+    return f32(*make_rays(seed, terrain_scene(hf), nray, (-m, -m, -size[3] - 1.0), (m, m, size[2] + 2.0)))
+
+
+def hfield_families(name, nrand=400):
+    """every ray family of terrain `name` in the field's frame: list of (family name, (P, V)); diagonals on A and B only (on C one in
+    eleven of them is non-robust, too close to the suites' cap of one in ten)"""
+    hf = terrain(name)
+    seed = TERRAINS[name][3] * 10
+    out = [("nodes", hfield_node_rays(hf)[:2]), ("row planes", hfield_line_rays(hf, 1, seed + 1)), ("column planes", hfield_line_rays(hf, 0, seed + 2))]
+    if name != "C":
+        out.append(("diagonals", hfield_diagonal_rays(hf, seed + 3)))
+    out += [("grazing", hfield_grazing_rays(hf, seed + 4)), ("random", hfield_random_rays(hf, seed + 5, nrand))]
+    return out
+
+
+# two height fields from two assets (C first: the second asset's data starts at 17 * 33), each tilted, side by side; a static box and
+# a free sphere stand on the first
+TWO_FIELDS_QUAT2 = tuple(np.array([0.93, -0.12, 0.1, 0.3]) / np.linalg.norm([0.93, -0.12, 0.1, 0.3]))
+
+
+def two_fields_spec():
+    """list of dicts as primitives_spec(), an hfield entry with its terrain's name under `terrain`"""
+    posC, posA = np.array([0.0, 0.0, 0.3]), np.array([12.0, 0.5, 0.6])
+    RC = quat2mat(HF_QUAT).reshape(3, 3)
+    hfC = terrain("C")
+
+    def on_c(x, y, lift):
+        return tuple(posC + RC @ np.array([x, y, float(hfield_height(hfC, np.array([x]), np.array([y]))[0]) + lift]))
+    return [dict(type=HFIELD, size=(0.0, 0.0, 0.0), pos=tuple(posC), quat=HF_QUAT, free=False, terrain="C"),
+            dict(type=HFIELD, size=(0.0, 0.0, 0.0), pos=tuple(posA), quat=TWO_FIELDS_QUAT2, free=False, terrain="A"),
+            dict(type=BOX, size=(0.3, 0.2, 0.25), pos=on_c(-1.3, 0.4, 0.45), quat=HF_QUAT, free=False),
+            dict(type=SPHERE, size=(0.3, 0, 0), pos=on_c(1.6, -0.5, 0.4), quat=(1.0, 0, 0, 0), free=True)]
+
+
+def two_fields_scene(spec=None):
+    spec = spec or two_fields_spec()
+    sc = scene_from_spec(spec)
+    sc["hfield"] = {g: terrain(s["terrain"]) for g, s in enumerate(spec) if s["type"] == HFIELD}
+    return sc
+
+
+def two_fields_rays(scene, nray=300, seed=71):
+    return f32(*make_rays(seed, scene, nray, (-6.0, -8.0, -3.0), (19.0, 8.0, 6.0)))
+
+
+def level_spec():
+    """an axis-aligned world: every solid type once, static and unrotated, round a scanner at the origin, on a bounded floor"""
+    return [dict(type=PLANE, size=(4.0, 4.0, 0.05), pos=(0.0, 0.0, 0.0), quat=(1.0, 0, 0, 0), free=False),
+            dict(type=BOX, size=(0.25, 0.15, 0.4), pos=(1.5, 0.0, 0.4), quat=(1.0, 0, 0, 0), free=False),
+            dict(type=CYLINDER, size=(0.18, 0.4, 0), pos=(0.0, 1.6, 0.4), quat=(1.0, 0, 0, 0), free=False),
+            dict(type=CAPSULE, size=(0.12, 0.3, 0), pos=(-1.5, 0.05, 0.45), quat=(1.0, 0, 0, 0), free=False),
+            dict(type=ELLIPSOID, size=(0.3, 0.18, 0.25), pos=(0.2, -1.5, 0.3), quat=(1.0, 0, 0, 0), free=False),
+            dict(type=SPHERE, size=(0.3, 0, 0), pos=(1.2, 1.2, 0.35), quat=(1.0, 0, 0, 0), free=False),
+            dict(type=SPHERE, size=(0.05, 0, 0), pos=(40.0, 40.0, 50.0), quat=(1.0, 0, 0, 0), free=True)]      # (a model needs a moving body)
+
+
+LEVEL_HEIGHTS = (0.2, 0.35, 0.5)
+
+
+def level_rays():
+    """a 360-beam horizontal fan (vec.z == 0) from the origin at three heights, then beams with two zero components: along +-x, +-y from
+    the scanner, +-z from there, and along the cylinder's and the capsule's axis (on it, and beside it through the cap) from above and
+    from below the floor"""
+    a = np.deg2rad(np.arange(360) + 0.25)
+    P = [np.stack([0 * a, 0 * a, 0 * a + h], axis=1) for h in LEVEL_HEIGHTS]
+    V = [np.stack([np.cos(a), np.sin(a), 0 * a], axis=1) * (0.5 + 0.5 * k) for k in range(3)]
+    ax = [((0, 0, 0.35), (1.0, 0, 0)), ((0, 0, 0.35), (-1.0, 0, 0)), ((0, 0, 0.35), (0, 2.0, 0)), ((0, 0, 0.35), (0, -0.5, 0)),
+          ((0, 0, 0.35), (0, 0, -1.0)), ((0, 0, 0.35), (0, 0, 1.0)),
+          ((0.0, 1.6, 2.0), (0, 0, -1.0)), ((0.05, 1.63, 2.0), (0, 0, -0.5)), ((0.05, 1.63, -1.0), (0, 0, 1.0)),       # the cylinder's axis
+          ((-1.5, 0.05, 2.0), (0, 0, -1.0)), ((-1.45, 0.08, 2.0), (0, 0, -2.0)), ((-1.5, 0.05, -1.0), (0, 0, 1.0)),      # the capsule's
+          ((1.2, 1.2, 3.0), (0, 0, -1.0)), ((0.2, -1.5, 3.0), (0, 0, -1.0)), ((1.5, 0.0, 3.0), (0, 0, -1.0)),
+          ((3.0, 1.2, 0.35), (-1.0, 0, 0)), ((0.2, 3.0, 0.3), (0, -1.0, 0))]
+    P.append(np.array([p for p, _ in ax], float)); V.append(np.array([v for _, v in ax], float))
+    return f32(np.vstack(P), np.vstack(V))
+
+
+def far_rays(scene, nray=130, seed=81):
+    """the lines of primitive_rays, each origin moved back along its ray to 20 .. 30 m from the world's origin"""
+    P, V = make_rays(seed, scene, nray, (-3.0, -2.0, 0.05), (3.0, 2.0, 3.0))
+    rng = np.random.default_rng(seed + 1)
+    U = V / np.linalg.norm(V, axis=1, keepdims=True)
+    R = rng.uniform(20.0, 30.0, size=nray)
+    pu = np.sum(P * U, axis=1)
+    s = pu + np.sqrt(pu * pu - np.sum(P * P, axis=1) + R * R)
+    return f32(P - s[:, None] * U, V)
+
+
+def extreme_points(t, s):
+    """the points of a geom farthest from its centre (geom frame): what a bounding sphere one ulp too tight would cut off"""
+    if t == BOX:
+        return np.array([[a * s[0], b * s[1], c * s[2]] for a in (-1, 1) for b in (-1, 1) for c in (-1, 1)], float)
+    if t == CYLINDER:
+        return np.array([[s[0] * np.cos(a), s[0] * np.sin(a), z * s[1]] for z in (-1, 1) for a in np.arange(8) * np.pi / 4])
+    if t == CAPSULE:
+        return np.array([[0, 0, s[0] + s[1]], [0, 0, -s[0] - s[1]]], float)
+    if t == ELLIPSOID:
+        return np.array([[sg * s[k] if j == k else 0.0 for j in range(3)] for k in range(3) for sg in (-1, 1)])
+    return np.zeros((0, 3))
+
+
+def extreme_point_rays(scene, per_point=4, seed=91):
+    """rays from random directions, 1 .. 2 m away, through 0.97 x every extreme point of every box, cylinder, capsule and ellipsoid:
+    (P, V, target geom [nray], distance of the point along the ray in units of |vec| [nray]); origins above the floor, outside every geom"""
+    rng = np.random.default_rng(seed)
+    P, V, G, D = [], [], [], []
+    for g in range(len(scene["type"])):
+        t = int(scene["type"][g]); R = scene["mat"][g].reshape(3, 3)
+        for q in extreme_points(t, scene["size"][g]):
+            w = scene["pos"][g] + R @ (0.97 * q)
+            k = 0
+            while k < per_point:
+                u = rng.normal(size=3); u /= np.linalg.norm(u)
+                d = rng.uniform(1.0, 2.0)
+                o = w - d * u
+                if o[2] < 0.05 or _is_inside_any(o[None], scene)[0]:
+                    continue
+                ln = rng.uniform(0.5, 2.0)
+                P.append(o); V.append(u * ln); G.append(g); D.append(d / ln); k += 1
+    P, V = f32(np.array(P), np.array(V))
+    return P, V, np.array(G), np.array(D)
+
+
+FRAME_FAMILIES = ["random", "zero x", "zero y", "zero z", "along x", "along y", "along z"]
+
+
+def frame_rays(t, s, family, dist, nray, seed):
+    """rays in the frame of one primitive (a plane included), origins `dist` metres away, rounded to float32.  random: aimed at a point
+    inside the geom (a plane: of its footprint); zero k: the same with component k of the origin moved to the target's, so that vec[k]
+    is exactly 0; along k: parallel to axis k, the other two coordinates spread over 1.2 times the geom's extent (some rays pass by)"""
+    rng = np.random.default_rng(seed)
+    ext = np.array([s[0] if s[0] > 0 else 1.0, s[1] if s[1] > 0 else 1.0, 0.0]) if t == PLANE else \
+        {SPHERE: np.full(3, s[0]), CAPSULE: np.array([s[0], s[0], s[0] + s[1]]), CYLINDER: np.array([s[0], s[0], s[1]])}.get(t, np.array(s, float))
+    T = rng.uniform(-1, 1, size=(nray, 3)) * ext * 0.8
+    u = rng.normal(size=(nray, 3))
+    if t == PLANE:
+        u[:, 2] = np.abs(u[:, 2]) + 0.05      # (from the front)
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    kind, _, axis = family.partition(" ")
+    k = "xyz".find(axis)
+    if kind == "along":
+        T = rng.uniform(-1, 1, size=(nray, 3)) * ext * 1.2
+        u = np.zeros((nray, 3)); u[:, k] = rng.choice([-1.0, 1.0], size=nray)
+    elif kind == "zero":
+        u[:, k] = 0.0
+        u /= np.linalg.norm(u, axis=1, keepdims=True)
+    P, T = f32(T + dist * u, T)
+    V = T - P
+    V *= (rng.uniform(0.5, 2.0, size=nray) / np.linalg.norm(V, axis=1))[:, None]
+    V = f32(V)
+    if kind == "zero":
+        V[:, k] = 0.0
+    elif kind == "along":
+        V[:, [j for j in range(3) if j != k]] = 0.0
+    return P, V
 
 
 def primitive_rays(scene, nray, seed=21):

@@ -410,3 +410,145 @@ def test_errors_launch_nothing(prim, lib):
         e.ray(P, Vz)
     assert call() == 0
     assert np.array_equal(dist, good_d) and np.array_equal(gid, good_g)
+
+
+# ------------------------------------------------------------------ 11. height fields with large cell indices, rays on grid lines
+def _add_terrain(lib, b, name, tag, pos, quat):
+    nrow, ncol, size, elev = rr.terrain(name)
+    el = (C.c_double * elev.size)(*elev.ravel())
+    h = lib.mjh_builder_add_hfield(b, b"terrain" + tag, nrow, ncol, D(*size), el)
+    assert h >= 0
+    assert lib.mjh_builder_add_hfield_geom(b, b"ground" + tag, 0, h, D(*pos), D(*quat), None, -1, -1, -1) >= 0
+
+
+def _far_body(lib, b):
+    bd = lib.mjh_builder_add_body(b, b"far", 0, D(40.0, 40.0, 50.0), None, 0.0)      # (a model needs a moving body; it is out of every ray's way)
+    lib.mjh_builder_add_joint(b, None, bd, 0, None, None, None, 0, 0, 0, 0, 0)
+    lib.mjh_builder_add_geom(b, b"fg", bd, rr.SPHERE, D(0.05, 0, 0), None, None, None, -1, -1, -1, -1)
+
+
+def _same_in_every_env(dist, gid):
+    """no per-env data: the other envs computed the very same numbers, so the reference is evaluated for env 0 only"""
+    for env in range(1, len(dist)):
+        assert np.array_equal(dist[env], dist[0]) and np.array_equal(gid[env], gid[0]), env
+
+
+@pytest.mark.parametrize("name", ["A", "B", "C"])
+def test_hfield_grid_lines(lib, name):
+    """an unrotated field at the world origin, rays rounded to float32: what the device sees lies on the grid line.  Rows / columns up
+    to index 38 (A: 40 x 9, B: 9 x 40), where the rounding of a cell coordinate is several times the 1e-6 the walk once allowed"""
+    import hfield_ref
+    b = lib.mjh_builder_create()
+    _add_terrain(lib, b, name, b"", (0, 0, 0), (1, 0, 0, 0))
+    _far_body(lib, b)
+    set_opt(lib, b, gravity=[0, 0, 0])
+    m = ms.Model(lib.mjh_builder_compile(b), lib)
+    lib.mjh_builder_destroy(b)
+    assert m.ray_skipped_geoms() == 0
+    e = ms.Engine(m, 4)
+    hf = hfield_ref.hfield_of(m, 0)
+    assert np.array_equal(hf[3], rr.terrain(name)[3]) and (hf[0], hf[1]) == rr.TERRAINS[name][:2]
+    scene = _device_scene(e, m, 0, hfield={0: hf})
+    assert np.array_equal(scene["pos"][0], np.zeros(3)) and np.array_equal(scene["mat"][0], np.eye(3).ravel()), "the frame rays are world rays"
+    for fam, rays in rr.hfield_families(name):
+        dist, gid = e.ray(*rays)
+        _same_in_every_env(dist, gid)
+        _check(f"terrain {name} {fam}", dist[0], gid[0], scene, rays)
+    P, V, rc = rr.hfield_node_rays(hf)
+    dist, gid = e.ray(P, V, n=1)
+    top = (P[:, 2] - hf[3][rc[:, 0], rc[:, 1]] * hf[2][2]) / -V[:, 2]
+    base = (P[:, 2] + hf[2][3]) / -V[:, 2]
+    assert (gid[0] == 0).all()
+    assert np.abs(dist[0] - top).max() <= TOL * max(1.0, top.max()), "a node query returns origin_z - elevation * size_z"
+    if name != "C":
+        assert (np.abs(dist[0] - top) < np.abs(dist[0] - base)).all(), "every interior node is hit on the top, not the base"
+    e.close()
+
+
+def test_hfield_two_assets_rotated(lib):
+    """two fields from two assets (C, then A: the second's data starts at 17 * 33), each at its own tilted pose, a static box and a
+    free sphere on the first: the asset offset, large cell indices through a rotation, the nearest of field and what stands on it"""
+    import hfield_ref
+    spec = rr.two_fields_spec()
+    b = lib.mjh_builder_create()
+    set_opt(lib, b, gravity=[0, 0, 0])
+    for k, g in enumerate(spec):
+        if g["type"] == rr.HFIELD:
+            _add_terrain(lib, b, g["terrain"], b"%d" % k, g["pos"], g["quat"])
+        elif g["free"]:
+            bd = lib.mjh_builder_add_body(b, b"free%d" % k, 0, D(*g["pos"]), D(*g["quat"]), 0.0)
+            lib.mjh_builder_add_joint(b, None, bd, 0, None, None, None, 0, 0, 0, 0, 0)
+            assert lib.mjh_builder_add_geom(b, b"g%d" % k, bd, g["type"], D(*g["size"]), None, None, None, -1, -1, -1, -1) >= 0
+        else:
+            assert lib.mjh_builder_add_geom(b, b"g%d" % k, 0, g["type"], D(*g["size"]), D(*g["pos"]), D(*g["quat"]), None, -1, -1, -1, -1) >= 0
+    m = ms.Model(lib.mjh_builder_compile(b), lib)
+    lib.mjh_builder_destroy(b)
+    assert m.ray_skipped_geoms() == 0
+    types = m.array("geom_type")
+    fields = [int(g) for g in np.nonzero(types == rr.HFIELD)[0]]
+    assert len(fields) == 2 and list(m.array("hfield_adr")[:2]) == [0, 17 * 33]
+    hfs = {g: hfield_ref.hfield_of(m, g) for g in fields}
+    assert (hfs[fields[0]][0], hfs[fields[1]][0]) == (17, 40)
+    e = ms.Engine(m, 4)
+    scene = _device_scene(e, m, 0, hfield=hfs)
+    rays = rr.two_fields_rays(scene)
+    dist, gid = e.ray(*rays)
+    _same_in_every_env(dist, gid)
+    _check("two fields", dist[0], gid[0], scene, rays)
+    hit = set(int(g) for g in gid[0] if g >= 0)
+    assert hit >= set(fields), "both fields are hit"
+    assert {int(types[g]) for g in hit} >= {rr.HFIELD, rr.BOX, rr.SPHERE}, "and both primitives on the first"
+    e.close()
+
+
+# ------------------------------------------------------------------ 12. unrotated geoms, rays with zero components
+def test_level_scan_in_an_axis_aligned_world(lib):
+    """a horizontal fan (vec.z == 0) and beams along the axes in a world of unrotated geoms: the v[k] == 0 branches of the slab test,
+    the cylinder caps' skip and the quadratic's a == 0 exit (a beam along the cylinder's / capsule's axis) on the device"""
+    spec = rr.level_spec()
+    m = _build(lib, spec)
+    e = ms.Engine(m, 4)
+    scene = _device_scene(e, m, 0)
+    rays = rr.level_rays()
+    P, V = rays
+    assert (V[:1080, 2] == 0).all() and ((V[1080:] == 0).sum(axis=1) == 2).all()
+    dist, gid = e.ray(*rays)
+    _same_in_every_env(dist, gid)
+    _check("level scan", dist[0], gid[0], scene, rays)
+    types = scene["type"]
+    zero = (V == 0).any(axis=1)
+    assert {int(types[g]) for g in gid[0][zero & (gid[0] >= 0)]} >= {rr.BOX, rr.CYLINDER, rr.CAPSULE, rr.ELLIPSOID, rr.SPHERE}
+    axis = gid[0][1080:]
+    assert {int(types[g]) for g in axis[axis >= 0]} >= {rr.PLANE, rr.BOX, rr.CYLINDER, rr.CAPSULE, rr.ELLIPSOID, rr.SPHERE}
+    cyl, cap = int(np.nonzero(types == rr.CYLINDER)[0][0]), int(np.nonzero(types == rr.CAPSULE)[0][0])
+    assert (axis[6:9] == cyl).all() and (axis[9:12] == cap).all(), "the beams along the cylinder's and the capsule's axis"
+    assert dist[0][1080 + 6] == pytest.approx(2.0 - 0.8, abs=1e-5) and dist[0][1080 + 9] == pytest.approx(2.0 - 0.45 - 0.3 - 0.12, abs=1e-5)
+    e.close()
+
+
+# ------------------------------------------------------------------ 13. far origins
+def test_far_origins(prim):
+    m, e, scene, _ = prim
+    rays = rr.far_rays(scene)
+    r = np.linalg.norm(rays[0], axis=1)
+    assert r.min() >= 19.99 and r.max() <= 30.01
+    dist, gid = e.ray(*rays)
+    _same_in_every_env(dist, gid)
+    _check("far origins", dist[0], gid[0], scene, rays)
+    assert (gid[0] >= 0).sum() >= 60
+
+
+# ------------------------------------------------------------------ 14. the bounding-sphere reject
+def test_bounding_sphere_reject_costs_no_hit(prim):
+    """rays through points at 0.97 x the extreme points of every box (corners), cylinder (rims), capsule (tips) and ellipsoid (axis
+    ends): each passes through its geom, so it hits that geom or a nearer one — a cull one ulp too tight shows as a miss here"""
+    m, e, scene, _ = prim
+    P, V, target, along = rr.extreme_point_rays(scene)
+    assert len(P) == 2 * 4 * (8 + 16 + 2 + 6)
+    dist, gid = e.ray(P, V)
+    _same_in_every_env(dist, gid)
+    _check("extreme points", dist[0], gid[0], scene, (P, V))
+    assert (gid[0] >= 0).all(), "no ray through a geom's extreme point misses"
+    assert ((gid[0] == target) | (dist[0] < along)).all(), "that geom or a nearer one"
+    assert (dist[0] <= along).all(), "... in front of the point the ray was aimed through"
+    assert (gid[0] == target).mean() >= 0.8

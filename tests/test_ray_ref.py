@@ -77,6 +77,27 @@ def test_hfield_row_column_order():
     assert d == pytest.approx(2.0 - rr.HF_ELEV[1, 1] * sz)
 
 
+def test_hfield_rays_on_grid_lines_agree_with_march():
+    """the edge slack of the triangle test: rays that lie in the plane of a grid line, pass through nodes along a diagonal, or come
+    straight down at nodes of a 9 x 9 field hit what marching the membership test finds — no ray falls between two triangles"""
+    e = rr.rolling(9, 9, 77)
+    hf = (9, 9, np.array([1.0, 0.8, 0.5, 0.2]), e)
+    P, V, rc = rr.hfield_node_rays(hf)
+    sets = [("nodes", (P, V)), ("row planes", rr.hfield_line_rays(hf, 1, 78, 60)), ("column planes", rr.hfield_line_rays(hf, 0, 79, 60)),
+            ("diagonals", rr.hfield_diagonal_rays(hf, 80, 60))]
+    scene = rr.terrain_scene(hf)
+    for name, (P, V) in sets:
+        ref = rr.geom_ray(rr.HFIELD, P, V, (0, 0, 0), hf)
+        rob = rr.robust((P, V), scene)
+        got = rr.march(rr.HFIELD, P, V, (0, 0, 0), hf)
+        print(f"{name}: {len(P)} rays, robust {int(rob.sum())}, hits {int((ref >= 0).sum())}")
+        assert rob.mean() >= 0.9, name
+        assert ((got >= 0) == (ref >= 0))[rob].all(), name
+        assert np.abs(got - ref)[rob & (ref >= 0)].max() <= 1e-6, name
+        if name == "nodes":
+            assert rob.all() and np.allclose(ref, (P[:, 2] - e[rc[:, 0], rc[:, 1]] * 0.5) / -V[:, 2], atol=1e-9)
+
+
 # ---- the generated ray sets of tests/test_gpu_ray.py at the scenes' nominal poses
 def _s24_scene(lib, env):
     m = ms.scene("s24")
@@ -109,6 +130,16 @@ def _sets(lib):
         yield "s24 env %d" % env, sc, rr.s24_rays(sc, 96)
     ms_ = _many_spheres_scene()
     yield "many spheres", ms_, rr.many_spheres_rays(ms_)
+    for name in ("A", "B", "C"):      # the grid-line families (unrotated field at the origin: the frame rays are world rays)
+        sc = rr.terrain_scene(rr.terrain(name))
+        for fam, rays in rr.hfield_families(name):
+            yield "terrain %s %s" % (name, fam), sc, rays
+    two = rr.two_fields_scene()
+    yield "two fields", two, rr.two_fields_rays(two)
+    level = rr.scene_from_spec(rr.level_spec())
+    yield "level scan", level, rr.level_rays()
+    yield "far origins", prim, rr.far_rays(prim)
+    yield "extreme points", prim, rr.extreme_point_rays(prim)[:2]
 
 
 def test_non_robust_share_of_every_ray_set(lib):
