@@ -162,6 +162,14 @@ typedef struct mjh_model {
   double* hfield_size;                          /* [4*nhfield]: radius_x, radius_y, elevation_z, base_z */
   double* hfield_data;                          /* [nhfielddata] */
   char** hfield_names;
+  /* ---- appended for ray casting against mesh geoms (older fields keep their offsets) ----
+   * the facets of the convex hull of each mesh's kept vertices (exactly the points of mesh_vert, so a ray sees the solid the narrow
+   * phase collides), coplanar facets merged: every distinct plane once.  A mesh whose kept vertices span no volume has
+   * mesh_planenum 0 (no ray sees it). */
+  int nmeshplane;
+  int *mesh_planeadr, *mesh_planenum;   /* [nmesh] */
+  double* mesh_plane;                   /* [4*nmeshplane]: unit outward normal n, offset d; inside is n.x <= d;
+                                           frame of mesh_vert (the mesh geom's own frame) */
 } mjh_model;
 
 /* ------------------------------------------------- model builder (host) */
@@ -223,6 +231,7 @@ int mjh_builder_add_sensor(mjh_builder*, const char* name, int type /* mjh_senso
 /* compile: derives inertias, qpos0, invweight0, meaninertia, rbound, pair list */
 mjh_model* mjh_builder_compile(mjh_builder*);
 void mjh_model_destroy(mjh_model*);
+/* (the mesh assets — mesh_vert and the hull planes — are shared by the copies of mjh_model_replicate) */
 /* Sub-wave packing for small models (nv of a few, a handful of bodies: the C1 / C3 / C5 scenes): `copies` independent
  * instances of every moving body tree in ONE model, sharing the static geometry (world / welded-to-world geoms) and
  * never colliding with each other.  An engine created from the result steps `copies` environments per wavefront:
@@ -436,7 +445,13 @@ int mjh_set_body_pose(mjh_engine*, int env, int body, const double pos[3], const
  *   sphere, capsule, ellipsoid, cylinder (flat caps), box: nearest non-negative root (an origin inside hits the far surface);
  *   height field: the solid the collision code uses (two triangles per cell sharing the diagonal (r,c)-(r+1,c+1), side walls and
  *     base down to -size[3]), hit at its nearest surface from any side;
- *   mesh geoms (and hfield geoms without an asset) are invisible: mjh_ray_skipped_geoms counts them.
+ *   mesh geoms: invisible by default (mode 0); with mjh_ray_set_mesh_mode(engine, 1) a mesh geom is hit at the nearest non-negative x
+ *     on its convex hull (mesh_plane: the hull of the kept vertices, the solid the narrow phase collides), and an origin inside hits
+ *     the far surface, like the other bounded types.  mj_ray itself intersects the mesh file's triangles: for a convex mesh the two
+ *     agree, for a non-convex one the ray sees the collision hull.  bodyexclude, flg_static, inactive slots and cutoff apply to
+ *     mesh geoms like any other.  A mesh geom's hull is that of the model's mesh_vert: per-env geom sizes do not rescale it, as they
+ *     do not in the narrow phase.
+ *   hfield geoms without an asset are invisible; mjh_ray_skipped_geoms counts what mode 0 cannot see.
  * A geom of a body whose spawn / destroy slot is inactive in an env is invisible there; geom sizes are the env's own where per-env
  * sizes are set (mjh_set_env_param).  Call-sequence rules are those of mjh_get_geom_state (a pending mjh_step1 is issued first and a
  * window hand-over is dropped); nothing of the envs' state, statistics or time is written. */
@@ -456,7 +471,11 @@ int mjh_ray(mjh_engine*, int env0, int n, int nray, const double* pnt, const dou
  * mjh_synchronize (a zero vec cannot be refused here: such a ray misses) */
 int mjh_ray_device(mjh_engine*, int env0, int n, int nray, const float* d_pnt, const float* d_vec,
                    const mjh_ray_options*, float* d_dist, int* d_geomid);
-int mjh_ray_skipped_geoms(const mjh_model*);     /* geoms no ray can see (mesh geoms, hfield geoms without an asset) */
+int mjh_ray_skipped_geoms(const mjh_model*);     /* geoms no ray can see in mesh mode 0 (mesh geoms, hfield geoms without an asset) */
+/* how the rays of this engine treat mesh geoms: 0 (default) invisible, 1 hit as the convex hull; any other mode returns MJH_ERR_ARG and
+ * changes nothing.  Takes effect with the next ray call (the geom table of the mode is uploaded on that call's stream order). */
+int mjh_ray_set_mesh_mode(mjh_engine*, int mode);
+int mjh_ray_get_mesh_mode(const mjh_engine*);
 
 /* zero-copy export for the single ROS state topic: packs time(1)+qpos(nq)+qvel(nv)
  * fp32 per env into a caller-provided DEVICE buffer [nenv*(1+nq+nv)] on the engine's

@@ -76,6 +76,9 @@ _ARRAYS4 = [
     ("hfield_nrow", "i", "nhfield"), ("hfield_ncol", "i", "nhfield"), ("hfield_adr", "i", "nhfield"),
     ("hfield_size", "d", "4*nhfield"), ("hfield_data", "d", "nhfielddata"),
 ]
+# appended for ray casting against mesh geoms (behind hfield_names): the hull planes of the kept vertices
+_INT_SIZES5 = ["nmeshplane"]
+_ARRAYS5 = [("mesh_planeadr", "i", "nmesh"), ("mesh_planenum", "i", "nmesh"), ("mesh_plane", "d", "4*nmeshplane")]
 
 
 class Model(C.Structure):
@@ -92,15 +95,17 @@ class Model(C.Structure):
         + [(n, C.c_int) for n in _INT_SIZES4]
         + [(n, c_int_p if t == "i" else c_double_p) for n, t, _ in _ARRAYS4]
         + [("hfield_names", C.POINTER(C.c_char_p))]
+        + [(n, C.c_int) for n in _INT_SIZES5]
+        + [(n, c_int_p if t == "i" else c_double_p) for n, t, _ in _ARRAYS5]
     )
 
     def array(self, name):
         """numpy copy of a model array."""
         import numpy as np
 
-        for n, t, expr in _ARRAYS + _ARRAYS2 + _ARRAYS3 + _ARRAYS4:
+        for n, t, expr in _ARRAYS + _ARRAYS2 + _ARRAYS3 + _ARRAYS4 + _ARRAYS5:
             if n == name:
-                ln = eval(expr, {}, {k: getattr(self, k) for k in _INT_SIZES + _INT_SIZES2 + _INT_SIZES4})
+                ln = eval(expr, {}, {k: getattr(self, k) for k in _INT_SIZES + _INT_SIZES2 + _INT_SIZES4 + _INT_SIZES5})
                 ptr = getattr(self, n)
                 if ln == 0 or not ptr:
                     return np.zeros(0, dtype=np.int32 if t == "i" else np.float64)
@@ -212,6 +217,8 @@ SYMBOLS = [
     ("mjh_ray", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, C.POINTER(RayOptions), c_double_p, c_int_p]),
     ("mjh_ray_device", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.POINTER(RayOptions), _vp, _vp]),
     ("mjh_ray_skipped_geoms", C.c_int, [Model_p]),
+    ("mjh_ray_set_mesh_mode", C.c_int, [_vp, C.c_int]),
+    ("mjh_ray_get_mesh_mode", C.c_int, [_vp]),
     ("mjh_export_state_device", C.c_int, [_vp, _vp]),
     ("mjh_state_stride", C.c_int, [_vp]),
     ("mjh_mirror_create", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(_vp)]),

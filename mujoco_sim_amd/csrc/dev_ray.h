@@ -10,17 +10,21 @@
 #define RAY_TILE 64   // rays per workgroup: one wavefront, one ray per lane
 #define RAY_PASS 64   // geom records one staging pass holds (one geom per lane)
 #define RAY_REC 20    // floats of a record: [0..2] world position, [3..11] rotation (row-major, world = R local), [12..14] the env's size,
-                      // [15] bounding radius, [16] type (int; -1: invisible in this env), [17] hfield id (int), [18] geom id (int), [19] pad
+                      // [15] bounding radius, [16] type (int; -1: invisible in this env), [17] hfield id / mesh id (int), [18] geom id (int), [19] pad
 
 struct RayHField { int nrow, ncol, adr, pad; float size[4]; };   // size: radius_x, radius_y, elevation_z, base_z
+
+struct RayMesh { int adr, num; float rbound, pad; };              // a mesh asset's planes [adr, adr + num) of RayArgs::planes; bounding radius of its vertices
 
 struct RayArgs {
   const float *gpos, *gmat;        // geom poses of the n envs as the position stage exported them: [n][3 ngeom], [n][9 ngeom]
   const float *xpos, *xquat;       // body poses [n][3 nbody], [n][4 nbody] (site >= 0 only)
   const float* size; long long size_stride;   // geom sizes: row of env `e` at size + e * size_stride (per-env tables), or stride 0 (the shared model)
   const unsigned* slot_mask; int sbase;       // spawn / destroy slots: bit b of slot_mask[env] = body sbase + b is inactive (null: none)
-  const int4* ginfo;               // [ngeom]: x type (-1: no ray sees it: mesh, hfield without an asset), y body, z 1 = static body, w hfield id
+  const int4* ginfo;               // [ngeom]: x type (-1: no ray sees it: hfield without an asset, mesh in mesh mode 0 or without planes), y body,
+                                   // z 1 = static body, w hfield id / mesh id
   const RayHField* hf; const float* hf_data;
+  const RayMesh* mesh; const float4* planes;   // mesh mode 1: [nmesh], [nmeshplane] (n.x, n.y, n.z, d: unit outward normal, inside is n.x <= d)
   const float *pnt, *vec;          // [nray][3], or [n][nray][3] with per_env
   float* dist; int* geomid;        // [n][nray]
   int env0, n, nray, ngeom, nbody;
@@ -125,6 +129,38 @@ RDEV float ray_box(const float* p, const float* v, const float* s) {
   float lo, hi;
   if (!ray_slabs(p, v, bmin, s, lo, hi) || hi < 0.0f) return -1.0f;
   return lo >= 0.0f ? lo : hi;       // an origin inside the box hits the far face
+}
+
+// Convex polyhedron given by its n facet planes (planes[k] = unit outward normal, offset d; inside is n.x <= d): the ray is clipped
+// against the half spaces.  With den = n.v and num = d - n.p a plane the ray runs towards from inside (den > 0) lowers the exit, one it
+// enters through (den < 0) raises the entry, and a ray parallel to a plane and outside it (den == 0, num < 0) misses.  The entry if it
+// is >= 0, else the exit (an origin inside hits the far surface, like the other bounded types).  n and the address of the planes
+// are wave-uniform in the kernel: the plane reads are scalar loads and the loop a scalar branch, a lane carries lo, hi and the two dot
+// products.  Planes go four at a time (one 64-byte scalar load); on the device the loop ends after a group once no lane of the wave
+// has lo <= hi left.  The engine pads every mesh's planes to a multiple of four with (0, 0, 0, 1) — den = 0, num = 1: no effect —, so
+// the tail loop is the host's.
+RDEV void ray_clip(const float* p, const float* v, const float4 pl, float& lo, float& hi) {
+  const float den = pl.x * v[0] + pl.y * v[1] + pl.z * v[2];
+  const float num = pl.w - (pl.x * p[0] + pl.y * p[1] + pl.z * p[2]);
+  const float t = num / (den != 0.0f ? den : 1.0f);      // (selects, not branches: the lanes of a wave disagree on the sign of den at most planes)
+  hi = den > 0.0f ? fminf(hi, t) : hi;
+  lo = den < 0.0f ? fmaxf(lo, t) : lo;
+  hi = (den == 0.0f && num < 0.0f) ? -3.0e38f : hi;
+}
+
+RDEV float ray_convex(const float* p, const float* v, const float4* __restrict__ planes, int n) {
+  float lo = -3.0e38f, hi = 3.0e38f;
+  int k = 0;
+  for (; k + 4 <= n; k += 4) {
+#pragma unroll
+    for (int j = 0; j < 4; j++) ray_clip(p, v, planes[k + j], lo, hi);
+#ifdef __HIP_DEVICE_COMPILE__
+    if (__builtin_amdgcn_ballot_w64(lo <= hi) == 0) return -1.0f;      // (wave-uniform: every lane has missed)
+#endif
+  }
+  for (; k < n; k++) ray_clip(p, v, planes[k], lo, hi);
+  if (!(lo <= hi)) return -1.0f;
+  return lo >= 0.0f ? lo : (hi >= 0.0f ? hi : -1.0f);
 }
 
 // Height field: the solid the prism narrow phase collides (step_kernel.h: hfield_pair) — over grid cell (r, c) the two triangles

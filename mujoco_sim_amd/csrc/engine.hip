@@ -111,6 +111,9 @@ struct mjh_engine {
   float pd_kp = 0, pd_kd = 0; float* pd_target = nullptr; bool pd_on = false;
   // ray casting (mjh_ray / mjh_ray_device, ray.hip): per-geom and per-hfield tables uploaded at the first call, staging of the host form
   int4* ray_ginfo = nullptr; RayHField* ray_hf = nullptr; float* ray_hfdata = nullptr; bool ray_ready = false;
+  // mesh mode (mjh_ray_set_mesh_mode): the geom table of mode 1 (mesh geoms typed MJH_GEOM_MESH with their mesh id; the mode-0 table itself
+  // in a model without hull planes), the per-mesh table and the fp32 planes — uploaded with the others; a mode change switches tables
+  int ray_mesh_mode = 0; int4* ray_ginfo_mesh = nullptr; RayMesh* ray_mesh = nullptr; float4* ray_planes = nullptr;
   float* ray_io = nullptr; size_t ray_io_floats = 0;
 };
 
@@ -1817,7 +1820,7 @@ extern "C" int mjh_debug_stop_at(mjh_engine* e, int stage, int with_inverse) {
 // position-stage launch of the env range (PH_FKONLY with XF_GEOM, plus XF_BODY for rays given in a site's frame) into the engine's
 // export scratch, exactly as fk_export issues it, then mjh_ray_kernel (ray.hip) on the same stream.  Nothing of the envs' state,
 // statistics or time is written.
-// what a ray can see of geom g: its type, or -1 (mesh geoms: the model keeps no faces; an hfield geom without an asset)
+// what a ray can see of geom g in mesh mode 0: its type, or -1 (mesh geoms; an hfield geom without an asset)
 static int ray_geom_type(const mjh_model* m, int g) {
   const int t = m->geom_type[g];
   if (t == MJH_GEOM_MESH) return -1;
@@ -1859,9 +1862,50 @@ static int ray_tables(mjh_engine* e) {
     HIPCHK(hipMemcpy(e->ray_hf, hf.data(), hf.size() * sizeof(RayHField), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(e->ray_hfdata, hd.data(), hd.size() * sizeof(float), hipMemcpyHostToDevice));
   }
+  e->ray_ginfo_mesh = e->ray_ginfo;
+  if (m->nmesh > 0 && m->nmeshplane > 0 && m->mesh_plane && m->mesh_planeadr && m->mesh_planenum && m->geom_dataid) {
+    // mode 1: a mesh geom whose asset has hull planes is typed MJH_GEOM_MESH, w = its mesh id (a mesh without volume stays invisible)
+    // (every mesh's planes padded to a multiple of four with planes that clip nothing: dev_ray.h, ray_convex)
+    std::vector<RayMesh> mt((size_t)m->nmesh);
+    std::vector<float4> pl;
+    pl.reserve((size_t)m->nmeshplane + 3 * (size_t)m->nmesh);
+    for (int i = 0; i < m->nmesh; i++) {
+      const int adr = m->mesh_planeadr[i], num = m->mesh_planenum[i];
+      const bool ok = adr >= 0 && num > 0 && (long long)adr + num <= m->nmeshplane;
+      double r2 = 0;
+      for (int k = 0; k < m->mesh_vertnum[i]; k++) { const double* x = m->mesh_vert + 3 * ((size_t)m->mesh_vertadr[i] + k); r2 = std::max(r2, x[0]*x[0] + x[1]*x[1] + x[2]*x[2]); }
+      mt[i].adr = (int)pl.size(); mt[i].num = 0; mt[i].rbound = (float)std::sqrt(r2); mt[i].pad = 0.0f;
+      if (!ok) continue;
+      for (int k = adr; k < adr + num; k++) pl.push_back(make_float4((float)m->mesh_plane[4*k], (float)m->mesh_plane[4*k+1], (float)m->mesh_plane[4*k+2], (float)m->mesh_plane[4*k+3]));
+      while (pl.size() % 4) pl.push_back(make_float4(0.0f, 0.0f, 0.0f, 1.0f));
+      mt[i].num = (int)pl.size() - mt[i].adr;
+    }
+    if (pl.empty()) pl.push_back(make_float4(0.0f, 0.0f, 0.0f, 1.0f));
+    bool any = false;
+    for (int g = 0; g < m->ngeom; g++) {
+      const int id = m->geom_dataid[g];
+      if (m->geom_type[g] == MJH_GEOM_MESH && id >= 0 && id < m->nmesh && mt[id].num > 0) { gi[g].x = MJH_GEOM_MESH; gi[g].w = id; any = true; }
+    }
+    if (any) {
+      rc = dev_alloc(e, &e->ray_ginfo_mesh, gi.size(), false);
+      if (!rc) rc = dev_alloc(e, &e->ray_mesh, mt.size(), false);
+      if (!rc) rc = dev_alloc(e, &e->ray_planes, pl.size(), false);
+      if (rc) return rc;
+      HIPCHK(hipMemcpy(e->ray_ginfo_mesh, gi.data(), gi.size() * sizeof(int4), hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(e->ray_mesh, mt.data(), mt.size() * sizeof(RayMesh), hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(e->ray_planes, pl.data(), pl.size() * sizeof(float4), hipMemcpyHostToDevice));
+    }
+  }
   e->ray_ready = true;
   return MJH_OK;
 }
+extern "C" int mjh_ray_set_mesh_mode(mjh_engine* e, int mode) {
+  ENG(e);
+  if (mode != 0 && mode != 1) { mjh_set_error("mjh_ray_set_mesh_mode: mode must be 0 or 1"); return MJH_ERR_ARG; }
+  e->ray_mesh_mode = mode;      // (both geom tables are resident: the next ray launch takes the mode's own by value)
+  return MJH_OK;
+}
+extern "C" int mjh_ray_get_mesh_mode(const mjh_engine* e) { return e ? e->ray_mesh_mode : 0; }
 // argument checks shared by both entry points: nothing is launched when one fails
 static int ray_check(const mjh_engine* e, int env0, int n, int nray, const void* pnt, const void* vec, const mjh_ray_options* o, const void* dist, const void* geomid) {
   if (env0 < 0 || n <= 0 || env0 + n > e->nenv) { mjh_set_error("mjh_ray: env range out of bounds"); return MJH_ERR_ARG; }
@@ -1897,7 +1941,8 @@ extern "C" int mjh_ray_device(mjh_engine* e, int env0, int n, int nray, const fl
   if (rc) return rc;
   if (e->S.p_geom_size) { A.size = e->S.p_geom_size; A.size_stride = e->S.p_stride; } else { A.size = e->dF + e->M.o_geom_size; A.size_stride = 0; }
   A.slot_mask = e->S.slot_mask; A.sbase = nb > 32 ? nb - 32 : 0;
-  A.ginfo = e->ray_ginfo; A.hf = e->ray_hf; A.hf_data = e->ray_hfdata;
+  A.ginfo = e->ray_mesh_mode ? e->ray_ginfo_mesh : e->ray_ginfo; A.hf = e->ray_hf; A.hf_data = e->ray_hfdata;
+  A.mesh = e->ray_mesh; A.planes = e->ray_planes;
   A.pnt = d_pnt; A.vec = d_vec; A.dist = d_dist; A.geomid = d_geomid;
   A.env0 = env0; A.n = n; A.nray = nray; A.ngeom = ng; A.nbody = nb;
   A.per_env = o.per_env ? 1 : 0; A.bodyexclude = o.bodyexclude; A.flg_static = o.flg_static ? 1 : 0; A.cutoff = o.cutoff > 0 ? (float)o.cutoff : 0.0f;

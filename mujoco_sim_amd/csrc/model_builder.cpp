@@ -41,6 +41,7 @@ struct BMesh {
   double pos[3], quat[4];          // own frame in the mesh file's frame
   double volume, inertia[3];       // unit density
   double rbound;
+  std::vector<double> plane;       // hull planes of `vert` (n, d per plane; hull_planes below), own frame
 };
 struct BEq { int type = MJH_EQ_JOINT; int j1 = -1, j2 = -1; double poly[5] = {0, 0, 0, 0, 0};        // joint coupling: joints j1, j2
               int b1 = 0, b2 = 0; double anchor[3] = {0, 0, 0}; double torquescale = 1; };       // connect / weld: bodies b1, b2
@@ -141,6 +142,130 @@ extern "C" int mjh_builder_add_geom(mjh_builder* b, const char* name, int body, 
   g.conaffinity = conaffinity >= 0 ? conaffinity : 1; g.density = density >= 0 ? density : 1000.0;   // negative = unset (MuJoCo default 1000); an explicit 0 is a massless geom
   b->geoms.push_back(g);
   return (int)b->geoms.size() - 1;
+}
+
+// ---- hull planes of a mesh's kept vertices (what a ray sees of a mesh geom: mjh_ray_set_mesh_mode)
+// out: (unit outward normal n, offset d) per DISTINCT facet plane of the convex hull of the points V, inside is n.x <= d; empty when
+// the points span no volume.  Written for robustness under coplanar and collinear input (CAD meshes: flat faces with many vertices,
+// vertices along straight edges), not for speed — the kept sets are a few hundred points:
+//   1. an incremental hull in which a point within `tolv` of a facet's plane SEES that facet.  A point on the hull's surface then
+//      re-fans every facet it is coplanar with, and no new triangle is degenerate: the apex would have to lie on the line of a
+//      horizon edge, i.e. in the plane of the facet behind that edge, which it then sees as well.  The triangulation is only a
+//      generator of candidate normals;
+//   2. every triangle's normal is pushed out to its supporting offset, the vertices within `tol` of that plane are collected, and
+//      the plane is fitted again to the widest triangle among them (farthest pair, then the vertex farthest from their line; the
+//      cross product in long double), so all triangles of one flat face arrive at the very same plane: it is stored once.
+// tol = 1e-10 and tolv = 1e-11 of the extent (the bounding box's diagonal): far above the fp64 rounding of coordinates rotated into the
+// principal axes (1e-16), far below the fp32 spacing of mesh file coordinates (1e-7).  A supporting set that is collinear within 1e-6
+// of the extent defines no plane (a triangle that thin is a sliver of the triangulation, not a face).
+static void hull_planes(const std::vector<double>& V, std::vector<double>& out) {
+  out.clear();
+  const int n = (int)V.size() / 3;
+  if (n < 4) return;
+  double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+  for (int i = 0; i < n; i++) for (int k = 0; k < 3; k++) { lo[k] = std::min(lo[k], V[3*i+k]); hi[k] = std::max(hi[k], V[3*i+k]); }
+  const double ext = std::sqrt((hi[0]-lo[0])*(hi[0]-lo[0]) + (hi[1]-lo[1])*(hi[1]-lo[1]) + (hi[2]-lo[2])*(hi[2]-lo[2]));
+  if (!(ext > 0) || !std::isfinite(ext)) return;
+  const double tol = 1e-10 * ext, tolv = 1e-11 * ext, thin = 1e-6 * ext;
+  auto sub = [&](int a, int b, double* r) { for (int k = 0; k < 3; k++) r[k] = V[3*a+k] - V[3*b+k]; };
+  auto dist2 = [&](int a, int b) { double r[3]; sub(a, b, r); return hm::dot3(r, r); };
+  // distance of point i from the line through a and b
+  auto line_dist = [&](int i, int a, int b) {
+    double e[3], r[3], c[3]; sub(b, a, e); sub(i, a, r); hm::cross(c, e, r);
+    const double le = std::sqrt(hm::dot3(e, e));
+    return le > 0 ? std::sqrt(hm::dot3(c, c)) / le : std::sqrt(hm::dot3(r, r));
+  };
+  // unit normal of triangle (a, b, c), long double inside; false: no area
+  auto tri_normal = [&](int a, int b, int c, double* nrm) {
+    long double e1[3], e2[3];
+    for (int k = 0; k < 3; k++) { e1[k] = (long double)V[3*b+k] - V[3*a+k]; e2[k] = (long double)V[3*c+k] - V[3*a+k]; }
+    const long double cx = e1[1]*e2[2] - e1[2]*e2[1], cy = e1[2]*e2[0] - e1[0]*e2[2], cz = e1[0]*e2[1] - e1[1]*e2[0];
+    const long double l = sqrtl(cx*cx + cy*cy + cz*cz);
+    if (!(l > 0)) { nrm[0] = nrm[1] = nrm[2] = 0; return false; }
+    nrm[0] = (double)(cx / l); nrm[1] = (double)(cy / l); nrm[2] = (double)(cz / l);
+    return true;
+  };
+  // ---- a first tetrahedron: lowest x, farthest from it, farthest from their line, farthest from their plane
+  int s0 = 0, s1 = 0, s2 = -1, s3 = -1;
+  for (int i = 1; i < n; i++) if (V[3*i] < V[3*s0]) s0 = i;
+  for (int i = 0; i < n; i++) if (dist2(i, s0) > dist2(s1, s0)) s1 = i;
+  double best = thin;
+  for (int i = 0; i < n; i++) { const double d = line_dist(i, s0, s1); if (d > best) { best = d; s2 = i; } }
+  if (s1 == s0 || s2 < 0) return;      // all points on one line
+  double n0[3];
+  if (!tri_normal(s0, s1, s2, n0)) return;
+  best = 1e-8 * ext;                   // flatter than this: no volume
+  for (int i = 0; i < n; i++) { double r[3]; sub(i, s0, r); const double d = std::fabs(hm::dot3(n0, r)); if (d > best) { best = d; s3 = i; } }
+  if (s3 < 0) return;
+  struct Face { int v[3]; double n[3], d; };
+  std::vector<Face> faces, next;
+  auto add_face = [&](std::vector<Face>& F, int a, int b, int c) {
+    Face f; f.v[0] = a; f.v[1] = b; f.v[2] = c;
+    tri_normal(a, b, c, f.n);          // (no area: n = 0, d = 0 — every point sees such a face, the next insertion removes it)
+    f.d = f.n[0]*V[3*a] + f.n[1]*V[3*a+1] + f.n[2]*V[3*a+2];
+    F.push_back(f);
+  };
+  auto above = [&](const Face& f, int i) { return f.n[0]*V[3*i] + f.n[1]*V[3*i+1] + f.n[2]*V[3*i+2] - f.d; };
+  {
+    const int t[4][4] = {{s0, s1, s2, s3}, {s0, s3, s1, s2}, {s0, s2, s3, s1}, {s1, s3, s2, s0}};
+    for (int k = 0; k < 4; k++) {
+      add_face(faces, t[k][0], t[k][1], t[k][2]);
+      if (above(faces.back(), t[k][3]) > 0) { faces.pop_back(); add_face(faces, t[k][0], t[k][2], t[k][1]); }
+    }
+  }
+  // ---- the other points, one at a time
+  std::vector<int> edge_stamp((size_t)n * n, -1);      // directed edge a -> b of a face the present point sees
+  std::vector<char> sees;
+  for (int i = 0; i < n; i++) {
+    if (i == s0 || i == s1 || i == s2 || i == s3) continue;
+    sees.assign(faces.size(), 0);
+    size_t nsee = 0;
+    for (size_t f = 0; f < faces.size(); f++) if (above(faces[f], i) > -tolv) { sees[f] = 1; nsee++; }
+    if (nsee == 0 || nsee == faces.size()) continue;   // inside the hull (or nothing to stand on)
+    for (size_t f = 0; f < faces.size(); f++) if (sees[f])
+      for (int k = 0; k < 3; k++) edge_stamp[(size_t)faces[f].v[k] * n + faces[f].v[(k+1)%3]] = i;
+    next.clear();
+    for (size_t f = 0; f < faces.size(); f++) {
+      if (!sees[f]) { next.push_back(faces[f]); continue; }
+      for (int k = 0; k < 3; k++) {
+        const int a = faces[f].v[k], b = faces[f].v[(k+1)%3];
+        if (edge_stamp[(size_t)b * n + a] != i) add_face(next, a, b, i);      // horizon edge: the face behind it stays
+      }
+    }
+    faces.swap(next);
+  }
+  // ---- candidate planes -> distinct facet planes
+  std::vector<int> S;
+  std::vector<std::vector<int>> keys;
+  for (const Face& f : faces) {
+    if (f.n[0] == 0 && f.n[1] == 0 && f.n[2] == 0) continue;
+    double nrm[3] = {f.n[0], f.n[1], f.n[2]}, d = 0;
+    int t0 = -1, t1 = -1, t2 = -1;
+    bool ok = true;
+    for (int pass = 0; pass < 2 && ok; pass++) {       // pass 0: the triangle's normal; pass 1: the normal fitted to its supporting set
+      d = -1e300;
+      for (int i = 0; i < n; i++) d = std::max(d, nrm[0]*V[3*i] + nrm[1]*V[3*i+1] + nrm[2]*V[3*i+2]);
+      S.clear();
+      for (int i = 0; i < n; i++) if (d - (nrm[0]*V[3*i] + nrm[1]*V[3*i+1] + nrm[2]*V[3*i+2]) <= tol) S.push_back(i);
+      if (pass == 1) break;
+      double far = -1;
+      for (size_t a = 0; a < S.size(); a++) for (size_t b = a + 1; b < S.size(); b++) { const double q = dist2(S[a], S[b]); if (q > far) { far = q; t0 = S[a]; t1 = S[b]; } }
+      if (t0 < 0) { ok = false; break; }
+      double h = thin;
+      for (int i : S) { const double q = line_dist(i, t0, t1); if (q > h) { h = q; t2 = i; } }
+      if (t2 < 0) { ok = false; break; }
+      double fit[3];
+      if (!tri_normal(t0, t1, t2, fit)) { ok = false; break; }
+      const double sg = hm::dot3(fit, nrm) < 0 ? -1.0 : 1.0;
+      for (int k = 0; k < 3; k++) nrm[k] = sg * fit[k];
+    }
+    if (!ok) continue;
+    // the fitted plane must still hold its own triangle (a sliver's normal can be far off: its supporting set is then another face's, or none)
+    if (std::find(S.begin(), S.end(), t0) == S.end() || std::find(S.begin(), S.end(), t1) == S.end() || std::find(S.begin(), S.end(), t2) == S.end()) continue;
+    if (std::find(keys.begin(), keys.end(), S) != keys.end()) continue;      // this face's plane is stored already
+    keys.push_back(S);
+    out.push_back(nrm[0]); out.push_back(nrm[1]); out.push_back(nrm[2]); out.push_back(d);
+  }
 }
 
 // ---- convex mesh assets
@@ -261,6 +386,7 @@ static int add_mesh_impl(mjh_builder* b, std::vector<double> v, const int* face,
     M.vert.push_back(v[3*i]); M.vert.push_back(v[3*i+1]); M.vert.push_back(v[3*i+2]);
     M.rbound = std::max(M.rbound, std::sqrt(v[3*i]*v[3*i] + v[3*i+1]*v[3*i+1] + v[3*i+2]*v[3*i+2]));
   }
+  hull_planes(M.vert, M.plane);
   b->meshes.push_back(M);
   return (int)b->meshes.size() - 1;
 }
@@ -614,10 +740,13 @@ extern "C" mjh_model* mjh_builder_compile(mjh_builder* B) {
       geom_solmix(ngeom), geom_solref(2*ngeom), geom_solimp(5*ngeom), geom_margin(ngeom), geom_gap(ngeom);
   std::vector<std::string> geom_names(ngeom);
   std::vector<int> geom_dataid(ngeom, -1), mesh_vertadr, mesh_vertnum;
-  std::vector<double> mesh_vert;
+  std::vector<double> mesh_vert, mesh_plane;
+  std::vector<int> mesh_planeadr, mesh_planenum;
   for (const BMesh& Mh : B->meshes) {
     mesh_vertadr.push_back((int)mesh_vert.size() / 3); mesh_vertnum.push_back((int)Mh.vert.size() / 3);
     mesh_vert.insert(mesh_vert.end(), Mh.vert.begin(), Mh.vert.end());
+    mesh_planeadr.push_back((int)mesh_plane.size() / 4); mesh_planenum.push_back((int)Mh.plane.size() / 4);
+    mesh_plane.insert(mesh_plane.end(), Mh.plane.begin(), Mh.plane.end());
   }
   for (int g = 0; g < ngeom; g++) {
     const BGeom& G = B->geoms[gorder[g]];
@@ -972,6 +1101,8 @@ extern "C" mjh_model* mjh_builder_compile(mjh_builder* B) {
   SETI(eq_type); SETI(eq_obj1id); SETI(eq_obj2id); SETI(eq_active); SETI(eq_data); SETI(eq_solref); SETI(eq_solimp);
   m->nmesh = (int)mesh_vertadr.size(); m->nmeshvert = (int)mesh_vert.size() / 3;
   SETI(geom_dataid); SETI(mesh_vertadr); SETI(mesh_vertnum); SETI(mesh_vert);
+  m->nmeshplane = (int)mesh_plane.size() / 4;
+  SETI(mesh_planeadr); SETI(mesh_planenum); SETI(mesh_plane);
 #undef SETI
   {   // height fields: elevation normalised to [0, 1] (minus the minimum, divided by the range when it is non-zero)
     const int nh = (int)B->hfields.size();
@@ -1124,6 +1255,10 @@ extern "C" mjh_model* mjh_model_replicate(const mjh_model* a, int G) {
   m->mesh_vertadr = ialloc(a->nmesh); m->mesh_vertnum = ialloc(a->nmesh); m->mesh_vert = dalloc((size_t)3 * a->nmeshvert);
   for (int i = 0; i < a->nmesh; i++) { m->mesh_vertadr[i] = a->mesh_vertadr[i]; m->mesh_vertnum[i] = a->mesh_vertnum[i]; }
   cpd(m->mesh_vert, a->mesh_vert, (size_t)3 * a->nmeshvert);
+  m->nmeshplane = a->nmeshplane;
+  m->mesh_planeadr = ialloc(a->nmesh); m->mesh_planenum = ialloc(a->nmesh); m->mesh_plane = dalloc((size_t)4 * a->nmeshplane);
+  for (int i = 0; i < a->nmesh; i++) { m->mesh_planeadr[i] = a->mesh_planeadr ? a->mesh_planeadr[i] : 0; m->mesh_planenum[i] = a->mesh_planenum ? a->mesh_planenum[i] : 0; }
+  if (a->mesh_plane) cpd(m->mesh_plane, a->mesh_plane, (size_t)4 * a->nmeshplane);
   m->body_names = dupnames(bnames); m->jnt_names = dupnames(jnames); m->geom_names = dupnames(gnames);
   m->body_mocapid = ialloc(NB);
   for (int b = 0; b < NB; b++) m->body_mocapid[b] = -1;
@@ -1143,7 +1278,8 @@ extern "C" void mjh_model_destroy(mjh_model* m) {
     m->pair_geom1, m->pair_geom2, m->eq_type, m->eq_obj1id, m->eq_obj2id, m->eq_active, m->eq_data, m->eq_solref, m->eq_solimp,
     m->geom_dataid, m->mesh_vertadr, m->mesh_vertnum, m->mesh_vert,
     m->site_bodyid, m->site_pos, m->site_quat, m->sensor_type, m->sensor_objid, m->sensor_adr, m->body_mocapid,
-    m->hfield_nrow, m->hfield_ncol, m->hfield_adr, m->hfield_size, m->hfield_data};
+    m->hfield_nrow, m->hfield_ncol, m->hfield_adr, m->hfield_size, m->hfield_data,
+    m->mesh_planeadr, m->mesh_planenum, m->mesh_plane};
   for (void* p : ptrs) std::free(p);
   auto freen = [](char** n, int c) { if (!n) return; for (int i = 0; i < c; i++) std::free(n[i]); std::free(n); };
   freen(m->body_names, m->nbody); freen(m->jnt_names, m->njnt); freen(m->geom_names, m->ngeom);

@@ -66,6 +66,7 @@ __global__ __launch_bounds__(RAY_TILE) void mjh_ray_kernel(const RayArgs A) {
       else if (gi.x == MJH_GEOM_ELLIPSOID) rb = fmaxf(s0, fmaxf(s1, s2));
       else if (gi.x == MJH_GEOM_CYLINDER) rb = sqrtf(s0*s0 + s1*s1);
       else if (gi.x == MJH_GEOM_BOX) rb = sqrtf(s0*s0 + s1*s1 + s2*s2);
+      else if (gi.x == MJH_GEOM_MESH) rb = A.mesh[gi.w].rbound;      // (of the model's mesh_vert: per-env sizes do not rescale a mesh, in the narrow phase neither)
       rec[15] = rb * 1.001f;     // (the reject below must never cost a hit: a sphere a little larger than the geom's)
       const bool slot_off = gi.y >= A.sbase && gi.y - A.sbase < 32 && ((slotmask >> (gi.y - A.sbase)) & 1u);
       const bool visible = gi.x >= 0 && gi.y != A.bodyexclude && (A.flg_static || !gi.z) && !slot_off;
@@ -100,6 +101,11 @@ __global__ __launch_bounds__(RAY_TILE) void mjh_ray_kernel(const RayArgs A) {
             case MJH_GEOM_ELLIPSOID: x = ray_ellipsoid(lp, lv, sz); break;
             case MJH_GEOM_CYLINDER: x = ray_cylinder(lp, lv, sz); break;
             case MJH_GEOM_BOX: x = ray_box(lp, lv, sz); break;
+            case MJH_GEOM_MESH: {      // the mesh id is wave-uniform: its table row and the planes come by scalar loads
+              const int mid = __builtin_amdgcn_readfirstlane(__float_as_int(rec[17]));
+              const RayMesh Mh = A.mesh[mid];
+              x = ray_convex(lp, lv, A.planes + Mh.adr, Mh.num);
+            } break;
             default: break;
           }
         }

@@ -42,7 +42,7 @@ class Model:
         return self.lib.mjh_name2id(self.ptr, objtype, name.encode())
 
     def ray_skipped_geoms(self):
-        """geoms no ray can see: mesh geoms and hfield geoms without an asset (mjh_ray_skipped_geoms)"""
+        """geoms no ray can see in mesh mode 0: mesh geoms and hfield geoms without an asset (mjh_ray_skipped_geoms)"""
         return self.lib.mjh_ray_skipped_geoms(self.ptr)
 
     def replicate(self, copies):
@@ -318,6 +318,15 @@ class Engine:
                 raise TypeError(f"unknown ray option {k!r}")
             setattr(o, k, v)
         return o
+
+    @property
+    def ray_mesh_mode(self):
+        """how rays treat mesh geoms: 0 (default) invisible, 1 hit as the convex hull of the kept vertices (mjh_ray_set_mesh_mode)"""
+        return self.lib.mjh_ray_get_mesh_mode(self.h)
+
+    @ray_mesh_mode.setter
+    def ray_mesh_mode(self, mode):
+        _chk(self.lib, self.lib.mjh_ray_set_mesh_mode(self.h, int(mode)), "mjh_ray_set_mesh_mode")
 
     def ray(self, pnt, vec, env0=0, n=None, **options):
         """rays pnt + x vec against the geoms of envs [env0, env0 + n): [nray, 3] arrays are one ray set shared by all envs, [n, nray, 3]
