@@ -116,7 +116,11 @@ struct Lay {
 // int tables nrow / ncol / adr per hfield, float tables size [4 per hfield] and the normalised elevations, all in the shared I / F buffers
 struct DHField { int has_hfield, o_hfield_nrow, o_hfield_ncol, o_hfield_adr, o_hfield_size, o_hfield_data; };
 
-struct DConst { DModel M; Lay L; DHField H; };
+// assemble-only launch of a patch model's window chain (WPRE instance 1; behind H for the same reason): slim != 0 — its LDS holds neither the pair
+// schedule nor own slots for bv / phi (they lie in the contact records, as in instance 2), and its base-row pool starts at float J instead of L.J
+struct DWpre { int slim, J; };
+
+struct DConst { DModel M; Lay L; DHField H; DWpre W; };
 
 // kernel phases
 enum { PH_STEP1 = 1, PH_INV = 2, PH_STEP2 = 4, PH_NOINT = 8, PH_FKONLY = 16, PH_MULM = 32, PH_RESET = 64,

@@ -64,8 +64,9 @@ struct mjh_engine {
   DModel M{};
   DState S{};
   Lay L{};
-  int lds_bytes = 0, lds_bytes_pre = 0;   // dynamic LDS per env of the step kernel; ... of its assemble-only instance (no patch pool: more envs per CU)
+  int lds_bytes = 0, lds_bytes_pre = 0;   // dynamic LDS per env of the step kernel; ... of its assemble-only instance (no patch pool: more envs per CU; HostPack's lds_bytes_wpre)
   DHField H{};                            // height fields (H.has_hfield: every launch of the step kernel takes an HF instance, hfield.hip)
+  DWpre W{};                              // patch models: where the assemble-only instance keeps its base rows and per-base vectors (derive_device_model)
   size_t dense_lds = 0, dense_solve_lds = 0;   // dynamic LDS of mjh_dense_build_kernel / mjh_dense_solve_kernel
   // dense solver on / off per cohort: mjh_order_kernel leaves "an env of the cohort swept long" in a host-mapped word (four slots per
   // cohort, one per rebuild of the launch order); the host adopts the word of TWO rebuilds ago after waiting for that kernel's event
@@ -262,7 +263,7 @@ static int pair_cap(int t1, int t2) {
 
 // Host-only derivation of the device model: packed tables, derived topology tables, capacities and the LDS
 // layout.  Needs no HIP device (mjh_query_lds_bytes uses it for capacity planning and in the CPU tests).
-struct HostPack { DModel M{}; Lay L{}; DHField H{}; std::vector<int> I; std::vector<float> F; int o_controlled = 0, o_odom = 0, lds_bytes = 0, lds_bytes_pre = 0; long long gstride = 0; };
+struct HostPack { DModel M{}; Lay L{}; DHField H{}; DWpre W{}; std::vector<int> I; std::vector<float> F; int o_controlled = 0, o_odom = 0, lds_bytes = 0, lds_bytes_pre = 0, lds_bytes_wpre = 0; long long gstride = 0; };      // lds_bytes_pre: an assemble-only launch's extent in the fused layout's own offsets; lds_bytes_wpre: what that launch allocates
 // Gauss-Seidel order of engines created afterwards (mjhip.h): 1 = mj_solPGS's own row order
 #define MJH_WINDOW_MAXCON 128    // contact capacity up to which a small free-body model steps through the window chain
 static int g_window_solver = getenv("MJH_WINDOW") ? (atoi(getenv("MJH_WINDOW")) != 0) : 1;
@@ -477,6 +478,7 @@ static void derive_device_model(const mjh_model* m, HostPack& hp, bool force_big
       else { L.cvel = vel; L.cacc = vel + a4; L.cfrc = vel + 2*a4; L.cfrcsub = vel + 3*a4; L.cdofdot = vel + 4*a4; }
     }
     const int extsz = (M.has_dim4 && !patch) ? nblkcap * SOLX_N : 0;   // (the patch sweep does not use the condim-4 extension)
+    int jpre = 0;      // LDS-resident layouts: the end of blkf — where a patch model's assemble-only instance puts its base rows (below)
     if (big) {
       L.blki = gput((long long)nblkcap * BLKI_STRIDE); L.blkf = gput((long long)nblkcap * BLKF_STRIDE);
       L.bv = gput((long long)nblkcap * 4); L.phi = gput((long long)nblkcap * 4); L.sched = gput((long long)nblkcap * 2); L.order = gput(nblkcap);
@@ -491,6 +493,7 @@ static void derive_device_model(const mjh_model* m, HostPack& hp, bool force_big
       static const bool slim2 = !(getenv("MJH_WPRE_SLIM2") && atoi(getenv("MJH_WPRE_SLIM2")) == 0);
       const bool wonly = M.window && !patch && slim2 && 8 * nblkcap <= M.maxcon * CON_STRIDE;
       if (wonly) hp.lds_bytes_pre = off * (int)sizeof(float);
+      jpre = off;
       if (2 * nblkcap * 4 <= k1_size && !keep) { L.bv = k1; L.phi = k1 + nblkcap * 4; }
       else { L.bv = put(nblkcap * 4); L.phi = put(nblkcap * 4); }
       L.sched = put(nblkcap * 2);
@@ -503,6 +506,18 @@ static void derive_device_model(const mjh_model* m, HostPack& hp, bool force_big
     }
     M.win_jsz = (int)jsz;
     if (!(M.window && !big && !patch)) hp.lds_bytes_pre = off * (int)sizeof(float);    // everything but the patch pool's own tail: what an assemble-only launch (window chain) touches
+    // Patch models on the window chain (S24): their assemble-only launch (WPRE instance 1) builds no pair schedule either and keeps bv / phi in
+    // the contact records like instance 2 (8 nblkcap <= maxcon CON_STRIDE: a patch model has no block but its contacts), so its base-row pool
+    // — in LDS still — starts where the fused kernel's layout has bv: S24 18192 -> 16592 B, 15 -> 13 granules of 1280 B.  Beside three window
+    // wavefronts (15 granules each) a CU then holds six of these workgroups instead of five: all 1365 of a cohort of the headline start at
+    // once, where about 30 started 5 - 25 us late and set the launch's end (56 -> 40 us, S24 14.95 -> 15.70 M env-steps/s, bitwise:
+    // profiles/assemble_round_summary.md).  Only W and this extent change: every offset in L, and with them every other instance, stay as
+    // they are.  MJH_WPRE_SLIM3=0: the former extent.
+    static const bool slim3 = !(getenv("MJH_WPRE_SLIM3") && atoi(getenv("MJH_WPRE_SLIM3")) == 0);
+    // (lds_bytes_pre — mjh_query_lds_bytes_assemble — stays the extent in the fused layout's offsets, an upper bound for these models; what the
+    //  launch allocates is lds_bytes_wpre, reported by mjh_debug_lds_layout)
+    int wpre_floats = 0;
+    if (slim3 && M.window && patch && !big && 8 * nblkcap <= M.maxcon * CON_STRIDE) { hp.W.slim = 1; hp.W.J = jpre; wpre_floats = jpre + (int)jsz; }
     if (patch) {
       // the pool: per patch of nr4 rows (a multiple of 4, at most 16) a record per row (20 floats between two bodies, 12 on one
       // body) + 16 floats per 4x4 tile of the lower triangle of AR: 16 .. 30 floats per row.  It takes the span of everything that
@@ -524,7 +539,8 @@ static void derive_device_model(const mjh_model* m, HostPack& hp, bool force_big
     L.site = m->nsite > 0 ? put(12 * m->nsite) : 0;        // world frame of every site: pos(3) + rotation(9)
     L.fext = m->nsensor > 0 ? put(6 * nb) : 0;             // external spatial force per body (mj_rnePostConstraint)
     // (the site frames / external forces sit behind the patch pool: an assemble-only launch of a model that has them gets the whole layout)
-    if (m->nsite > 0 || m->nsensor > 0) hp.lds_bytes_pre = off * (int)sizeof(float);
+    if (m->nsite > 0 || m->nsensor > 0) { hp.lds_bytes_pre = off * (int)sizeof(float); wpre_floats = 0; }
+    hp.lds_bytes_wpre = wpre_floats ? wpre_floats * (int)sizeof(float) : hp.lds_bytes_pre;
     if (big) {   // hand-over vectors of the three-launch step (non-negative offsets into the scratch slice)
       auto graw = [&](int n) { long long o = goff; goff += ((std::max(n, 1) + 3) / 4) * 4; return (int)o; };
       L.g_a0 = graw(nv); L.g_minv = graw(nv); L.g_qvel = graw(nv); L.g_smooth = graw(nv); L.g_qacc = graw(nv); L.g_meta = graw(8); L.g_qM = graw(m->nM);
@@ -596,7 +612,8 @@ extern "C" int mjh_debug_lds_layout(const mjh_model* m, char* out, int cap) {
 #undef X
   t += "total " + std::to_string(hp.L.total) + "\nlds_bytes " + std::to_string(hp.lds_bytes) + "\nlds_bytes_pre " + std::to_string(hp.lds_bytes_pre) +
        "\nk1_floats " + std::to_string(hp.M.k1_floats) + "\nmaxcon " + std::to_string(hp.M.maxcon) + "\nmaxblk " + std::to_string(hp.M.maxblk) +
-       "\nrowW " + std::to_string(hp.M.rowW) + "\nnstage " + std::to_string(hp.M.nstage) + "\nbig " + std::to_string((int)hp.M.big) + "\n";
+       "\nrowW " + std::to_string(hp.M.rowW) + "\nnstage " + std::to_string(hp.M.nstage) + "\nbig " + std::to_string((int)hp.M.big) +
+       "\nlds_bytes_wpre " + std::to_string(hp.M.window ? hp.lds_bytes_wpre : 0) + "\n";      // what the window chain's assemble-only launch allocates (0: the model does not take it)
   const int n = std::min((int)t.size(), cap - 1);
   std::memcpy(out, t.data(), (size_t)n); out[n] = 0;
   return n;
@@ -629,7 +646,7 @@ extern "C" int mjh_create(const mjh_model* m, int nenv, int device, void* stream
   e->model = m; e->nenv = nenv; e->device = device; e->stream = (hipStream_t)stream;
 
   HostPack hp; derive_fitting(m, hp);
-  e->M = hp.M; e->L = hp.L; e->H = hp.H; e->lds_bytes = hp.lds_bytes; e->lds_bytes_pre = hp.lds_bytes_pre; e->o_controlled = hp.o_controlled; e->o_odom = hp.o_odom;
+  e->M = hp.M; e->L = hp.L; e->H = hp.H; e->W = hp.W; e->lds_bytes = hp.lds_bytes; e->lds_bytes_pre = hp.lds_bytes_wpre; e->o_controlled = hp.o_controlled; e->o_odom = hp.o_odom;
   DModel& M = e->M; std::vector<int>& I = hp.I; std::vector<float>& F = hp.F;
   e->hI = I;
   if (dev_alloc(e, &e->dI, I.size(), false) || dev_alloc(e, &e->dF, F.size(), false)) { mjh_destroy(e); return MJH_ERR_NO_DEVICE; }
@@ -639,7 +656,7 @@ extern "C" int mjh_create(const mjh_model* m, int nenv, int device, void* stream
   M.I = e->dI; M.F = e->dF;
 
   {
-    DConst hc; hc.M = e->M; hc.L = e->L; hc.H = e->H;
+    DConst hc; hc.M = e->M; hc.L = e->L; hc.H = e->H; hc.W = e->W;
     if (dev_alloc(e, &e->dC, 1, false)) { mjh_destroy(e); return MJH_ERR_NO_DEVICE; }
     HIPCHK(hipMemcpyAsync(e->dC, &hc, sizeof hc, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));

@@ -20,6 +20,22 @@
 // per-stage instruction counts are differences of the hardware counters of launches that stop at successive stages)
 #define PROF(k) do { if ((xflags & XF_PROF) && lane == 0) S.x_prof[(size_t)blockIdx.x * PROF_STRIDE + (k)] = (long long)__builtin_amdgcn_s_memtime(); \
                      if (((xflags >> 8) & 15) == (k) && (k) > 0) return; } while (0)
+// Probe build (-DMJH_ASM_PROBE, never the default library): where and when the workgroups of an assemble-only launch of the window chain ran.  The
+// env's stats slot receives, instead of the contact count and the sweep count (nothing on the device reads [0]; the launch order reads [2] only for
+// an env without a cost hint; the window kernel of a probe build leaves both alone): [0] the workgroup's start on the 100 MHz wall clock — the one
+// clock that is comparable across CUs and XCDs, low 31 bits; the host subtracts the launch's earliest start —, [2] SIMD (2 bits) | CU, SH, SE of
+// HW_ID (8 bits) << 2 | XCC_ID (3 bits) << 10 | duration in ticks of 10 ns << 13.  tools/assemble_rounds.py reads them.
+#ifdef MJH_ASM_PROBE
+#define ASM_PROBE_BEGIN() const long long asm_probe_t0 = (long long)__builtin_amdgcn_s_memrealtime()
+#define ASM_PROBE_STORE() do { if (WPRE != 0 && lane == 0) { \
+    const int hw = (int)__builtin_amdgcn_s_getreg(63492), xcc = (int)__builtin_amdgcn_s_getreg(63508) & 7; \
+    const long long dt = (long long)__builtin_amdgcn_s_memrealtime() - asm_probe_t0; \
+    S.stats[4*env] = (int)(asm_probe_t0 & 0x7fffffff); \
+    S.stats[4*env+2] = ((hw >> 4) & 3) | (((hw >> 8) & 0xff) << 2) | (xcc << 10) | ((int)(dt < 0 ? 0 : (dt > 0x3ffff ? 0x3ffff : dt)) << 13); } } while (0)
+#else
+#define ASM_PROBE_BEGIN() do {} while (0)
+#define ASM_PROBE_STORE() do {} while (0)
+#endif
 #define MINIMP 0.0001f
 #define MAXIMP 0.9999f
 
@@ -950,6 +966,10 @@ __global__ __launch_bounds__(64, MJH_STEP_WAVES_T) void mjh_step_kernel(const DC
 #endif
   static_assert(alignof(DState) <= alignof(const DConst*), "the descriptor follows the first argument in the kernel-argument segment without padding");
   const DState& S = MJH_LAZY_STATE ? *(const DState*)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + sizeof(const DConst*)) : S_arg;
+  ASM_PROBE_BEGIN();
+#ifdef MJH_WPRE_PRIO      // (experiment builds: wave priority 0 .. 3 of the assemble-only instances, whose waves share their SIMDs with older window wavefronts)
+  if constexpr (WPRE != 0) __builtin_amdgcn_s_setprio(MJH_WPRE_PRIO);
+#endif
   // model descriptor + LDS layout live in device memory (uploaded once): uniform scalar loads on demand instead
   // of a by-value kernarg struct that the lambdas below would force into a private (scratch) copy
   const DModel& M = C->M;
@@ -1002,6 +1022,9 @@ __global__ __launch_bounds__(64, MJH_STEP_WAVES_T) void mjh_step_kernel(const DC
   // ... and the per-base scratch vectors bv / phi (velocity stage: J qvel; mj_inverse: J qacc and the base forces) in the contact records, which
   // nothing reads once the rows are made (the last reader is the row-parameter stage): this instance's LDS ends in front of their own slots (engine.hip)
   if constexpr (WPRE == 2) if (8 * max(M.maxblk, 1) <= M.maxcon * CON_STRIDE) { s_bv = s_con; s_phi = s_con + 4 * max(M.maxblk, 1); }
+  // patch models (up to 64 contacts): the same for bv / phi, and the base-row pool — still in LDS — moves up into the span that their slots and the
+  // pair schedule hold in the fused kernel's layout (this instance builds no schedule): S24 18192 -> 16592 B, 15 -> 13 LDS granules (engine.hip)
+  if constexpr (WPRE == 1) if (C->W.slim) { s_bv = s_con; s_phi = s_con + 4 * max(M.maxblk, 1); s_J = lds + C->W.J; s_B = s_J; }
   float* s_stage = s_J;  // raw-contact staging aliases the (not yet built) base-row storage
   const int rowW = M.rowW;
 
@@ -2566,6 +2589,7 @@ step_again:      // (a backward goto instead of a `for`: the instances without t
                 // (split API: the counts of THIS step are what mjh_get_stats / mjh_get_field see between the two halves, as after a plain mj_step1)
                 if (lane == 0 && wdefer) { S.stats[4*env] = ncon; S.stats[4*env+1] = nefc; S.stats[4*env+2] = 0; S.stats[4*env+3] |= flags & 0xff; }
                 if (lane == 0) { int* wh = (int*)wb; wh[0] = nrow; wh[1] = ncon; wh[2] = nefc; wh[3] = flags; wh[4] = (S.win64 > 0 && M.win_nvt == 24 && nrow > S.win64 && nrow <= (M.win_maxw > 16 ? 64 * (WN64_NW + WN64_NT) : 64 * WN64_NW)) ? 2 : ((S.win32 > 0 && M.win_nvt == 24 && nrow > S.win32 && nrow <= 32 * WN32_NW) ? 1 : 0); wh[5] = (wdefer && nrow == 0) ? 1 : 0; }   // [5]: an env without rows that the window kernel integrates (split API)
+                ASM_PROBE_STORE();
                 return;
               }
               // (more rows than the window kernel takes: this env finishes the step here, in patch form)
@@ -3151,6 +3175,7 @@ step_again:      // (a backward goto instead of a `for`: the instances without t
     S.time[env] = time;
     S.stats[4*env] = ncon; S.stats[4*env+1] = nefc; S.stats[4*env+2] = niter; S.stats[4*env+3] = ((S.stats[4*env+3] | flags) & 0xff) | (cost_hint << 8);
   }
+  ASM_PROBE_STORE();
   PROF(15);
   if ((xflags & XF_PROF) && lane == 0) S.x_prof[(size_t)blockIdx.x * PROF_STRIDE + 17] = (long long)__builtin_amdgcn_s_memrealtime();
 }

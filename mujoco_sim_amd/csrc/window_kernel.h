@@ -10,6 +10,13 @@
 #define WN_STAT0(x) (x)
 #endif
 
+// (probe build of the assemble launch, step_kernel.h: stats [0] and [2] are that launch's)
+#ifdef MJH_ASM_PROBE
+#define WN_STATS(env, ncon, nefc, niter) S.stats[4 * env + 1] = nefc
+#else
+#define WN_STATS(env, ncon, nefc, niter) S.stats[4 * env] = WN_STAT0(ncon); S.stats[4 * env + 1] = nefc; S.stats[4 * env + 2] = niter
+#endif
+
 #ifdef WN_PROF_CLK
 __shared__ long long wn_t0;      // (probe build: the wavefront's start clock)
 #endif
@@ -253,7 +260,7 @@ DEV void wn_finish_wide(const DModel& M, const DState& S, float* const wb, const
   if (dl_lane && q == 0) {
     S.time[env] += M.timestep_d;
     const int cost_hint = wn_cost_hint(M, nwin16, niter);
-    S.stats[4 * env] = WN_STAT0(wh[1]); S.stats[4 * env + 1] = wh[2]; S.stats[4 * env + 2] = niter;
+    WN_STATS(env, wh[1], wh[2], niter);
     S.stats[4 * env + 3] = ((S.stats[4 * env + 3] | flags) & 0xff) | (cost_hint << 8);
   }
 }
@@ -1103,7 +1110,7 @@ __global__ __launch_bounds__(64, 1) void mjh_window_kernel(const DConst* __restr
     S.time[env] += M.timestep_d;
     // launch-order hint: sweeps x windows in units of the fused kernel's hint (patch_pgs.h: about four instructions)
     const int cost_hint = wn_cost_hint(M, nwin, niter);
-    S.stats[4 * env] = WN_STAT0(wh[1]); S.stats[4 * env + 1] = wh[2]; S.stats[4 * env + 2] = niter;
+    WN_STATS(env, wh[1], wh[2], niter);
     S.stats[4 * env + 3] = ((S.stats[4 * env + 3] | flags) & 0xff) | (cost_hint << 8);
   }
 #undef WN_FOR_WINDOWS

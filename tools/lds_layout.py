@@ -22,7 +22,7 @@ def show(model, label):
     arrs = [(k, v) for k, v in kv if k not in tail]
     lds = sorted([(v, k) for k, v in arrs if v >= 0])
     print(f"== {label}: total {tail['total']} floats, lds_bytes {tail['lds_bytes']} ({-(-tail['lds_bytes'] // 1280)} granules -> {128 // -(-tail['lds_bytes'] // 1280)} per CU), "
-          f"assemble-only {tail['lds_bytes_pre']} B, k1 {tail['k1_floats']}, maxcon {tail['maxcon']}, maxblk {tail['maxblk']}, rowW {tail['rowW']}, nstage {tail['nstage']}, big {tail['big']}")
+          f"assemble-only {tail['lds_bytes_pre']} B (the launch allocates {tail.get('lds_bytes_wpre', tail['lds_bytes_pre'])} B), k1 {tail['k1_floats']}, maxcon {tail['maxcon']}, maxblk {tail['maxblk']}, rowW {tail['rowW']}, nstage {tail['nstage']}, big {tail['big']}")
     offs = sorted(set(v for v, _ in lds)) + [tail["total"]]
     for o, nxt in zip(offs[:-1], offs[1:]):
         names = [k for v, k in lds if v == o]
