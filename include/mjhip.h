@@ -170,6 +170,14 @@ typedef struct mjh_model {
   int *mesh_planeadr, *mesh_planenum;   /* [nmesh] */
   double* mesh_plane;                   /* [4*nmeshplane]: unit outward normal n, offset d; inside is n.x <= d;
                                            frame of mesh_vert (the mesh geom's own frame) */
+  /* ---- appended for depth cameras (older fields keep their offsets) ----
+   * <camera mode="fixed">: a frame attached to a body; MuJoCo's convention: the camera looks along its -z, +x is right, +y is up.
+   * mjh_depth renders from it (below); resolution, sensor attributes, near planes and the other modes are not modelled. */
+  int ncam;
+  int* cam_bodyid;              /* [ncam] */
+  double *cam_pos, *cam_quat;   /* [3 ncam], [4 ncam]: camera frame in its body */
+  double* cam_fovy;             /* [ncam] vertical field of view, degrees */
+  char** cam_names;
 } mjh_model;
 
 /* ------------------------------------------------- model builder (host) */
@@ -228,6 +236,9 @@ int mjh_builder_set_mocap(mjh_builder*, int body);
 /* <site> and <sensor><force site=.../><torque site=.../> */
 int mjh_builder_add_site(mjh_builder*, const char* name, int body, const double pos[3], const double quat[4]);
 int mjh_builder_add_sensor(mjh_builder*, const char* name, int type /* mjh_sensor */, int site);
+/* <camera> (fixed mode): returns the camera id.  pos / quat NULL: the identity (quat is normalised); fovy <= 0: MuJoCo's default of 45
+ * degrees; fovy >= 180 or a bad body: MJH_ERR_ARG */
+int mjh_builder_add_camera(mjh_builder*, const char* name, int body, const double pos[3], const double quat[4], double fovy);
 /* compile: derives inertias, qpos0, invweight0, meaninertia, rbound, pair list */
 mjh_model* mjh_builder_compile(mjh_builder*);
 void mjh_model_destroy(mjh_model*);
@@ -240,7 +251,7 @@ void mjh_model_destroy(mjh_model*);
  * continue until the slowest instance has converged), `time`, the statistics row and the bad-state reset.  Contact
  * and row capacities scale with `copies`.  Returns a new model (mjh_model_destroy) or NULL. */
 mjh_model* mjh_model_replicate(const mjh_model* m, int copies);
-int mjh_name2id(const mjh_model*, int objtype /*0 body,1 joint,2 geom,3 site,4 sensor*/, const char* name);
+int mjh_name2id(const mjh_model*, int objtype /*0 body,1 joint,2 geom,3 site,4 sensor,5 camera*/, const char* name);
 const char* mjh_id2name(const mjh_model*, int objtype, int id);
 
 /* MJCF-subset loader: replaces load_XML -> mj_loadXML (include/mujoco_sim/mj_util.h:185-193) for the element
@@ -476,6 +487,36 @@ int mjh_ray_skipped_geoms(const mjh_model*);     /* geoms no ray can see in mesh
  * changes nothing.  Takes effect with the next ray call (the geom table of the mode is uploaded on that call's stream order). */
 int mjh_ray_set_mesh_mode(mjh_engine*, int mode);
 int mjh_ray_get_mesh_mode(const mjh_engine*);
+
+/* Depth images: every env's view through a camera of the model, as tiled depth / segmentation images (the observation vision
+ * policies train on).  The rays are generated on the device from the camera's intrinsics and its body's pose in each env: no ray
+ * buffer is uploaded, and a camera on a moving body follows it per env.
+ *   Pixel (i, j) is row i from the top, column j from the left; its ray starts at the camera origin and goes through the pixel's
+ *   centre: in the camera frame d = (a t (2 (j + 1/2) / W - 1), t (1 - 2 (i + 1/2) / H), -1) with t = tan(fovy / 2), a = W / H.
+ *   d.z = -1, so the ray parameter of the hit (in units of |d|) is the depth along the optical axis, what a depth buffer holds
+ *   (range = 0); range = 1 multiplies it by |d|: the Euclidean distance from the camera origin.  A miss is depth -1, geomid -1.
+ *   Everything else is mjh_ray's on the same engine: the semantics per geom type (a camera inside a geom sees its far surface),
+ *   inactive slots, per-env geom sizes, mjh_ray_set_mesh_mode (it governs depth images too), the lower geom id on an exact fp32
+ *   tie, and the call-sequence rules (a pending mjh_step1 goes out first, a window hand-over is dropped).  Nothing of state,
+ *   statistics, warm start or time is written.
+ *   cull: each 8 x 8 pixel tile walks only the bounded geoms whose bounding sphere touches the tile's cone; cull = 0 makes every
+ *   tile visit every geom.  The two give the same bits (the cull may never cost a hit).
+ * A model without cameras, a camera or body id out of range, a non-positive size (or n * width * height of 2^30 or more), an env range
+ * out of bounds or a NULL depth pointer return MJH_ERR_ARG and launch nothing. */
+typedef struct mjh_depth_options {
+  int camera;          /* camera id */
+  int width, height;   /* pixels, each >= 1; n * width * height below 2^30 */
+  int bodyexclude;     /* geoms of this body are invisible; -1: none (MuJoCo renders the camera's own body: -1 is the default) */
+  int flg_static;      /* as mjh_ray_options */
+  int range;           /* 0: depth along the optical axis (what a depth buffer holds); 1: Euclidean distance from the camera origin */
+  int cull;            /* 1 (default): tile culling on; 0: every tile visits every geom -- same results bit for bit (debug / test) */
+  double cutoff;       /* > 0: a reported value beyond it is a miss (far plane); <= 0: none */
+} mjh_depth_options;
+void mjh_depth_default_options(mjh_depth_options*);   /* 0, 64, 64, -1, 1, 0, 1, 0 */
+/* device pointers; enqueued on the engine's stream, no synchronisation; d_geomid may be NULL.  options may be NULL (the defaults) */
+int mjh_depth_device(mjh_engine*, int env0, int n, const mjh_depth_options*, float* d_depth /*[n][height][width]*/, int* d_geomid);
+/* host pointers (fp32 images; geomid may be NULL): calls the device form through an engine-owned staging buffer and synchronises */
+int mjh_depth(mjh_engine*, int env0, int n, const mjh_depth_options*, float* depth, int* geomid);
 
 /* zero-copy export for the single ROS state topic: packs time(1)+qpos(nq)+qvel(nv)
  * fp32 per env into a caller-provided DEVICE buffer [nenv*(1+nq+nv)] on the engine's

@@ -79,6 +79,9 @@ _ARRAYS4 = [
 # appended for ray casting against mesh geoms (behind hfield_names): the hull planes of the kept vertices
 _INT_SIZES5 = ["nmeshplane"]
 _ARRAYS5 = [("mesh_planeadr", "i", "nmesh"), ("mesh_planenum", "i", "nmesh"), ("mesh_plane", "d", "4*nmeshplane")]
+# appended for depth cameras (behind mesh_plane)
+_INT_SIZES6 = ["ncam"]
+_ARRAYS6 = [("cam_bodyid", "i", "ncam"), ("cam_pos", "d", "3*ncam"), ("cam_quat", "d", "4*ncam"), ("cam_fovy", "d", "ncam")]
 
 
 class Model(C.Structure):
@@ -97,15 +100,18 @@ class Model(C.Structure):
         + [("hfield_names", C.POINTER(C.c_char_p))]
         + [(n, C.c_int) for n in _INT_SIZES5]
         + [(n, c_int_p if t == "i" else c_double_p) for n, t, _ in _ARRAYS5]
+        + [(n, C.c_int) for n in _INT_SIZES6]
+        + [(n, c_int_p if t == "i" else c_double_p) for n, t, _ in _ARRAYS6]
+        + [("cam_names", C.POINTER(C.c_char_p))]
     )
 
     def array(self, name):
         """numpy copy of a model array."""
         import numpy as np
 
-        for n, t, expr in _ARRAYS + _ARRAYS2 + _ARRAYS3 + _ARRAYS4 + _ARRAYS5:
+        for n, t, expr in _ARRAYS + _ARRAYS2 + _ARRAYS3 + _ARRAYS4 + _ARRAYS5 + _ARRAYS6:
             if n == name:
-                ln = eval(expr, {}, {k: getattr(self, k) for k in _INT_SIZES + _INT_SIZES2 + _INT_SIZES4 + _INT_SIZES5})
+                ln = eval(expr, {}, {k: getattr(self, k) for k in _INT_SIZES + _INT_SIZES2 + _INT_SIZES4 + _INT_SIZES5 + _INT_SIZES6})
                 ptr = getattr(self, n)
                 if ln == 0 or not ptr:
                     return np.zeros(0, dtype=np.int32 if t == "i" else np.float64)
@@ -122,6 +128,10 @@ class LoadOptions(C.Structure):
 
 class RayOptions(C.Structure):
     _fields_ = [("site", C.c_int), ("bodyexclude", C.c_int), ("flg_static", C.c_int), ("per_env", C.c_int), ("cutoff", C.c_double)]
+
+class DepthOptions(C.Structure):
+    _fields_ = [("camera", C.c_int), ("width", C.c_int), ("height", C.c_int), ("bodyexclude", C.c_int), ("flg_static", C.c_int),
+                ("range", C.c_int), ("cull", C.c_int), ("cutoff", C.c_double)]
 
 
 # every symbol include/mjhip.h declares: (name, restype, argtypes)
@@ -153,6 +163,7 @@ SYMBOLS = [
     ("mjh_builder_add_eq_weld", C.c_int, [_vp, C.c_int, C.c_int, c_double_p, C.c_double]),
     ("mjh_builder_set_mocap", C.c_int, [_vp, C.c_int]),
     ("mjh_builder_add_site", C.c_int, [_vp, C.c_char_p, C.c_int, c_double_p, c_double_p]),
+    ("mjh_builder_add_camera", C.c_int, [_vp, C.c_char_p, C.c_int, c_double_p, c_double_p, C.c_double]),
     ("mjh_builder_add_sensor", C.c_int, [_vp, C.c_char_p, C.c_int, C.c_int]),
     ("mjh_builder_compile", Model_p, [_vp]),
     ("mjh_model_destroy", None, [Model_p]),
@@ -219,6 +230,9 @@ SYMBOLS = [
     ("mjh_ray_skipped_geoms", C.c_int, [Model_p]),
     ("mjh_ray_set_mesh_mode", C.c_int, [_vp, C.c_int]),
     ("mjh_ray_get_mesh_mode", C.c_int, [_vp]),
+    ("mjh_depth_default_options", None, [C.POINTER(DepthOptions)]),
+    ("mjh_depth", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(DepthOptions), _vp, _vp]),
+    ("mjh_depth_device", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(DepthOptions), _vp, _vp]),
     ("mjh_export_state_device", C.c_int, [_vp, _vp]),
     ("mjh_state_stride", C.c_int, [_vp]),
     ("mjh_mirror_create", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(_vp)]),

@@ -16,6 +16,7 @@
 #include "../../include/mjhip.h"
 #include "step_kernel.h"
 #include "dev_ray.h"
+#include "dev_depth.h"
 
 void mjh_set_error(const std::string& s);  // model_builder.cpp
 hipError_t mjh_launch_window(hipStream_t st, int nvt, int grid, size_t lds, const DConst* dC, const DState& S, int env0, int n, int nl, int wxf, int n32, int n64);   // window.hip
@@ -1998,6 +1999,80 @@ extern "C" int mjh_ray(mjh_engine* e, int env0, int n, int nray, const double* p
   HIPCHK(hipMemcpyAsync(geomid, d_gid, nout * sizeof(int), hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   for (size_t i = 0; i < nout; i++) dist[i] = (double)hd[i];
+  return MJH_OK;
+}
+
+// ---- depth images (mjh_depth / mjh_depth_device, depth.hip): the launch chain of mjh_ray_device with a site — the position-stage launch
+// of the env range (PH_FKONLY, XF_GEOM | XF_BODY) into the export scratch, then mjh_depth_kernel on the same stream.  The camera's world
+// pose is formed on the device from its body's exported pose; the tables are the ones ray_tables() uploads.
+extern "C" void mjh_depth_default_options(mjh_depth_options* o) {
+  if (!o) return;
+  o->camera = 0; o->width = 64; o->height = 64; o->bodyexclude = -1; o->flg_static = 1; o->range = 0; o->cull = 1; o->cutoff = 0.0;
+}
+// argument checks shared by both entry points: nothing is launched when one fails
+static int depth_check(const mjh_engine* e, int env0, int n, const mjh_depth_options& o, const void* depth) {
+  const mjh_model* m = e->model;
+  if (m->ncam <= 0) { mjh_set_error("mjh_depth: the model has no camera"); return MJH_ERR_ARG; }
+  if (o.camera < 0 || o.camera >= m->ncam) { mjh_set_error("mjh_depth: camera id out of range"); return MJH_ERR_ARG; }
+  if (o.bodyexclude < -1 || o.bodyexclude >= m->nbody) { mjh_set_error("mjh_depth: bodyexclude out of range"); return MJH_ERR_ARG; }
+  if (env0 < 0 || n <= 0 || env0 + n > e->nenv) { mjh_set_error("mjh_depth: env range out of bounds"); return MJH_ERR_ARG; }
+  if (o.width <= 0 || o.height <= 0 || (long long)o.width * o.height * n > 0x3fffffffLL) { mjh_set_error("mjh_depth: width and height must be positive (and n * width * height below 2^30)"); return MJH_ERR_ARG; }
+  if (!depth) { mjh_set_error("mjh_depth: null pointer"); return MJH_ERR_ARG; }
+  return MJH_OK;
+}
+extern "C" int mjh_depth_device(mjh_engine* e, int env0, int n, const mjh_depth_options* opt, float* d_depth, int* d_geomid) {
+  ENG(e);
+  mjh_depth_options o; mjh_depth_default_options(&o);
+  if (opt) o = *opt;
+  int rc = depth_check(e, env0, n, o, d_depth);
+  if (!rc) rc = ray_tables(e);
+  if (rc) return rc;
+  const mjh_model* m = e->model;
+  const int ng = e->M.ngeom, nb = e->M.nbody;
+  const size_t fg = (size_t)n * 3 * ng, fm = (size_t)n * 9 * ng, fx = (size_t)n * 3 * nb, fq = (size_t)n * 4 * nb;
+  rc = ensure_scratch(e, fg + fm + fx + fq);
+  if (rc) return rc;
+  DepthArgs A{};
+  A.gpos = e->scratch; A.gmat = e->scratch + fg; A.xpos = e->scratch + fg + fm; A.xquat = e->scratch + fg + fm + fx;
+  {
+    StateGuard guard(&e->S);
+    e->S.x_gpos = e->scratch; e->S.x_gmat = e->scratch + fg; e->S.x_xpos = e->scratch + fg + fm; e->S.x_xquat = e->scratch + fg + fm + fx;
+    rc = launch(e, env0, n, 1, PH_FKONLY, XF_GEOM | XF_BODY);
+  }
+  if (rc) return rc;
+  if (e->S.p_geom_size) { A.size = e->S.p_geom_size; A.size_stride = e->S.p_stride; } else { A.size = e->dF + e->M.o_geom_size; A.size_stride = 0; }
+  A.slot_mask = e->S.slot_mask; A.sbase = nb > 32 ? nb - 32 : 0;
+  A.ginfo = e->ray_mesh_mode ? e->ray_ginfo_mesh : e->ray_ginfo; A.hf = e->ray_hf; A.hf_data = e->ray_hfdata;
+  A.mesh = e->ray_mesh; A.planes = e->ray_planes;
+  A.depth = d_depth; A.geomid = d_geomid;
+  A.env0 = env0; A.n = n; A.width = o.width; A.height = o.height; A.ngeom = ng; A.nbody = nb;
+  A.bodyexclude = o.bodyexclude; A.flg_static = o.flg_static ? 1 : 0; A.range = o.range ? 1 : 0; A.cull = o.cull ? 1 : 0;
+  A.cutoff = o.cutoff > 0 ? (float)o.cutoff : 0.0f;
+  A.cam_body = m->cam_bodyid[o.camera];
+  for (int k = 0; k < 3; k++) A.cam_pos[k] = (float)m->cam_pos[3 * o.camera + k];
+  for (int k = 0; k < 4; k++) A.cam_quat[k] = (float)m->cam_quat[4 * o.camera + k];
+  A.scale = (float)(std::tan(0.5 * m->cam_fovy[o.camera] * 3.14159265358979323846 / 180.0) / (double)o.height);
+  HIPCHK(mjh_launch_depth(e->stream, A));
+  return MJH_OK;
+}
+extern "C" int mjh_depth(mjh_engine* e, int env0, int n, const mjh_depth_options* opt, float* depth, int* geomid) {
+  ENG(e);
+  mjh_depth_options o; mjh_depth_default_options(&o);
+  if (opt) o = *opt;
+  int rc = depth_check(e, env0, n, o, depth);
+  if (rc) return rc;
+  const size_t nout = (size_t)n * o.width * o.height, need = 2 * nout;      // the staging buffer of mjh_ray serves both
+  if (need > e->ray_io_floats) {
+    if (e->ray_io) { HIPCHK(hipStreamSynchronize(e->stream)); HIPCHK(hipFree(e->ray_io)); e->ray_io = nullptr; e->ray_io_floats = 0; }
+    HIPCHK(hipMalloc((void**)&e->ray_io, need * sizeof(float)));
+    e->ray_io_floats = need;
+  }
+  float* const d_depth = e->ray_io; int* const d_gid = (int*)(e->ray_io + nout);
+  rc = mjh_depth_device(e, env0, n, &o, d_depth, geomid ? d_gid : nullptr);
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(depth, d_depth, nout * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+  if (geomid) HIPCHK(hipMemcpyAsync(geomid, d_gid, nout * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
   return MJH_OK;
 }
 

@@ -3,7 +3,7 @@
 // the step path: <compiler angle autolimits>, <option timestep gravity impratio iterations tolerance>,
 // root <default> (<geom>, <joint>), <worldbody>/<body> trees with <inertial>, <joint> (free, ball, hinge, slide),
 // <freejoint>, <geom> (plane, sphere, capsule, cylinder, box, ellipsoid, mesh: binary / ASCII STL and OBJ assets become convex hulls), gravcomp,
-// <contact><exclude>, <equality><joint polycoef> / <weld> / <connect>, <body mocap>, <site>, <sensor><force> / <torque>.  Everything is translated into mjh_builder_* calls; physics
+// <contact><exclude>, <equality><joint polycoef> / <weld> / <connect>, <body mocap>, <site>, <camera> (fixed mode; quat | euler | xyaxes, fovy), <sensor><force> / <torque>.  Everything is translated into mjh_builder_* calls; physics
 // defaults follow MuJoCo's documented defaults (angle = degree, hinge axis 0 0 1, geom type sphere, ...).
 // <asset><hfield> (inline elevation or MuJoCo's binary file; PNG files are skipped with their geoms) and hfield geoms on static bodies.
 // Not handled (reported in the returned note, mjh_load_note): tendons, actuators, PNG height fields, sensors other than force / torque.
@@ -151,6 +151,7 @@ struct Loader {
   }
   std::string note, basedir, meshdir;   // directory of the file being read (empty for a string), <compiler meshdir>
   int nameless = 0;
+  int ncamera = 0;      // cameras loaded so far: a nameless one is camera<id>
 
   double ang(double v) const { return degree ? v * 3.14159265358979323846 / 180.0 : v; }
   bool orientation(const Node& n, double* quat) {   // quat | euler (xyz) ; returns false if neither
@@ -309,7 +310,26 @@ struct Loader {
         const int id = mjh_builder_add_site(b, name.c_str(), body, pos, quat);
         if (id < 0) return false;
         site_id[name] = id;
-      } else if (c->tag != "light" && c->tag != "camera") note += "ignored <" + c->tag + ">; ";
+      } else if (c->tag == "camera") {
+        // fixed cameras only (an absent mode is "fixed"); resolution and sensor attributes are not read
+        std::string name = c->get("name") ? c->get("name") : ("camera" + std::to_string(ncamera));
+        if (c->get("mode") && std::string(c->get("mode")) != "fixed") { note += "skipped <camera " + name + " mode=\"" + c->get("mode") + "\"> (only fixed cameras are loaded); "; continue; }
+        double pos[3] = {0, 0, 0}, quat[4] = {1, 0, 0, 0}, fovy = 0, xy[6];
+        nums(c->get("pos"), pos, 3); nums(c->get("fovy"), &fovy, 1);
+        if (!orientation(*c, quat) && nums(c->get("xyaxes"), xy, 6) == 6) {
+          // xyaxes: x normalised, y made orthogonal to x and normalised, z = x cross y
+          double x[3] = {xy[0], xy[1], xy[2]}, y[3] = {xy[3], xy[4], xy[5]}, z[3];
+          if (hm::normalize3(x) < 1e-12) { mjh_set_error("<camera " + name + ">: xyaxes x axis is zero"); return false; }
+          const double d = hm::dot3(x, y);
+          for (int k = 0; k < 3; k++) y[k] -= d * x[k];
+          if (hm::normalize3(y) < 1e-12) { mjh_set_error("<camera " + name + ">: xyaxes axes are parallel"); return false; }
+          hm::cross(z, x, y);
+          const double R[9] = {x[0], y[0], z[0], x[1], y[1], z[1], x[2], y[2], z[2]};
+          hm::mat2quat(quat, R);
+        }
+        if (mjh_builder_add_camera(b, name.c_str(), body, pos, quat, fovy) < 0) return false;
+        ncamera++;
+      } else if (c->tag != "light") note += "ignored <" + c->tag + ">; ";
     }
     return true;
   }

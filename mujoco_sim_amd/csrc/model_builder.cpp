@@ -47,6 +47,7 @@ struct BEq { int type = MJH_EQ_JOINT; int j1 = -1, j2 = -1; double poly[5] = {0,
               int b1 = 0, b2 = 0; double anchor[3] = {0, 0, 0}; double torquescale = 1; };       // connect / weld: bodies b1, b2
 struct BSite { std::string name; int body; double pos[3], quat[4]; };
 struct BSensor { std::string name; int type, site; };
+struct BCamera { std::string name; int body; double pos[3], quat[4], fovy; };
 
 }  // namespace
 
@@ -64,6 +65,7 @@ struct mjh_builder {
   std::vector<BEq> eqs;
   std::vector<BSite> sites;
   std::vector<BSensor> sensors;
+  std::vector<BCamera> cameras;
   std::vector<int> mocap;       // builder body ids flagged <body mocap="true">
 };
 
@@ -555,6 +557,14 @@ extern "C" int mjh_builder_add_site(mjh_builder* b, const char* name, int body, 
   for (int i = 0; i < 3; i++) x.pos[i] = pos ? pos[i] : 0;
   if (quat) { for (int i = 0; i < 4; i++) x.quat[i] = quat[i]; hm::normalize4(x.quat); } else { x.quat[0] = 1; x.quat[1] = x.quat[2] = x.quat[3] = 0; }
   b->sites.push_back(x); return (int)b->sites.size() - 1;
+}
+extern "C" int mjh_builder_add_camera(mjh_builder* b, const char* name, int body, const double pos[3], const double quat[4], double fovy) {
+  if (body < 0 || body >= (int)b->bodies.size()) { g_err = "add_camera: bad body"; return MJH_ERR_ARG; }
+  if (!(fovy < 180.0)) { g_err = "add_camera: fovy must be below 180 degrees"; return MJH_ERR_ARG; }
+  BCamera x; x.name = name ? name : ""; x.body = body; x.fovy = fovy > 0 ? fovy : 45.0;      // (MuJoCo's default)
+  for (int i = 0; i < 3; i++) x.pos[i] = pos ? pos[i] : 0;
+  if (quat) { for (int i = 0; i < 4; i++) x.quat[i] = quat[i]; hm::normalize4(x.quat); } else { x.quat[0] = 1; x.quat[1] = x.quat[2] = x.quat[3] = 0; }
+  b->cameras.push_back(x); return (int)b->cameras.size() - 1;
 }
 extern "C" int mjh_builder_add_sensor(mjh_builder* b, const char* name, int type, int site) {
   if (site < 0 || site >= (int)b->sites.size()) { g_err = "add_sensor: bad site"; return MJH_ERR_ARG; }
@@ -1139,6 +1149,19 @@ extern "C" mjh_model* mjh_builder_compile(mjh_builder* B) {
     m->body_mocapid = dup(body_mocapid);
     m->site_names = dupnames(site_names); m->sensor_names = dupnames(sensor_names);
   }
+  {   // cameras: frame in the body, body ids renumbered as the sites' are
+    const int ncam = (int)B->cameras.size();
+    std::vector<int> cam_bodyid(ncam); std::vector<double> cam_pos(3*ncam), cam_quat(4*ncam), cam_fovy(ncam); std::vector<std::string> cam_names(ncam);
+    for (int i = 0; i < ncam; i++) {
+      const BCamera& C = B->cameras[i];
+      cam_bodyid[i] = newid[C.body]; cam_names[i] = C.name; cam_fovy[i] = C.fovy;
+      for (int k = 0; k < 3; k++) cam_pos[3*i+k] = C.pos[k];
+      for (int k = 0; k < 4; k++) cam_quat[4*i+k] = C.quat[k];
+    }
+    m->ncam = ncam;
+    m->cam_bodyid = dup(cam_bodyid); m->cam_pos = dup(cam_pos); m->cam_quat = dup(cam_quat); m->cam_fovy = dup(cam_fovy);
+    m->cam_names = dupnames(cam_names);
+  }
   return m;
 }
 
@@ -1147,6 +1170,7 @@ extern "C" mjh_model* mjh_model_replicate(const mjh_model* a, int G) {
   if (!a || G < 1) { g_err = "mjh_model_replicate: bad arguments"; return nullptr; }
   if (a->nsite || a->nsensor || a->nmocap) { g_err = "mjh_model_replicate: models with sites, sensors or mocap bodies are not packed"; return nullptr; }
   if (a->nhfield > 0) { g_err = "mjh_model_replicate: models with height fields are not packed"; return nullptr; }
+  if (a->ncam > 0) { g_err = "mjh_model_replicate: models with cameras are not packed"; return nullptr; }
   for (int e = 0; e < a->neq; e++) if (a->eq_type[e] != MJH_EQ_JOINT) { g_err = "mjh_model_replicate: connect / weld equalities are not packed"; return nullptr; }
   const int nb = a->nbody, nj = a->njnt, nv = a->nv, nq = a->nq, ng = a->ngeom, nt = a->ntree, ne = a->neq, np = a->npair, nM = a->nM;
   std::vector<int> moving_b, moving_g;
@@ -1279,26 +1303,27 @@ extern "C" void mjh_model_destroy(mjh_model* m) {
     m->geom_dataid, m->mesh_vertadr, m->mesh_vertnum, m->mesh_vert,
     m->site_bodyid, m->site_pos, m->site_quat, m->sensor_type, m->sensor_objid, m->sensor_adr, m->body_mocapid,
     m->hfield_nrow, m->hfield_ncol, m->hfield_adr, m->hfield_size, m->hfield_data,
-    m->mesh_planeadr, m->mesh_planenum, m->mesh_plane};
+    m->mesh_planeadr, m->mesh_planenum, m->mesh_plane, m->cam_bodyid, m->cam_pos, m->cam_quat, m->cam_fovy};
   for (void* p : ptrs) std::free(p);
   auto freen = [](char** n, int c) { if (!n) return; for (int i = 0; i < c; i++) std::free(n[i]); std::free(n); };
   freen(m->body_names, m->nbody); freen(m->jnt_names, m->njnt); freen(m->geom_names, m->ngeom);
   freen(m->site_names, m->nsite); freen(m->sensor_names, m->nsensor); freen(m->hfield_names, m->nhfield);
+  freen(m->cam_names, m->ncam);
   std::free(m);
 }
 
 extern "C" int mjh_name2id(const mjh_model* m, int objtype, const char* name) {
   if (!m || !name) return -1;
-  char** t = objtype == 0 ? m->body_names : objtype == 1 ? m->jnt_names : objtype == 2 ? m->geom_names : objtype == 3 ? m->site_names : m->sensor_names;
-  int n = objtype == 0 ? m->nbody : objtype == 1 ? m->njnt : objtype == 2 ? m->ngeom : objtype == 3 ? m->nsite : m->nsensor;
-  if (!t || objtype < 0 || objtype > 4) return -1;     // a model assembled without name tables
+  char** t = objtype == 0 ? m->body_names : objtype == 1 ? m->jnt_names : objtype == 2 ? m->geom_names : objtype == 3 ? m->site_names : objtype == 5 ? m->cam_names : m->sensor_names;
+  int n = objtype == 0 ? m->nbody : objtype == 1 ? m->njnt : objtype == 2 ? m->ngeom : objtype == 3 ? m->nsite : objtype == 5 ? m->ncam : m->nsensor;
+  if (!t || objtype < 0 || objtype > 5) return -1;     // a model assembled without name tables
   for (int i = 0; i < n; i++) if (t[i] && std::strcmp(t[i], name) == 0) return i;
   return -1;
 }
 extern "C" const char* mjh_id2name(const mjh_model* m, int objtype, int id) {
   if (!m) return nullptr;
-  char** t = objtype == 0 ? m->body_names : objtype == 1 ? m->jnt_names : objtype == 2 ? m->geom_names : objtype == 3 ? m->site_names : m->sensor_names;
-  int n = objtype == 0 ? m->nbody : objtype == 1 ? m->njnt : objtype == 2 ? m->ngeom : objtype == 3 ? m->nsite : m->nsensor;
-  if (!t || objtype < 0 || objtype > 4 || id < 0 || id >= n) return nullptr;
+  char** t = objtype == 0 ? m->body_names : objtype == 1 ? m->jnt_names : objtype == 2 ? m->geom_names : objtype == 3 ? m->site_names : objtype == 5 ? m->cam_names : m->sensor_names;
+  int n = objtype == 0 ? m->nbody : objtype == 1 ? m->njnt : objtype == 2 ? m->ngeom : objtype == 3 ? m->nsite : objtype == 5 ? m->ncam : m->nsensor;
+  if (!t || objtype < 0 || objtype > 5 || id < 0 || id >= n) return nullptr;
   return t[id];
 }

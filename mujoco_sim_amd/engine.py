@@ -31,7 +31,7 @@ class Model:
 
     def __getattr__(self, name):
         c = self.__dict__.get("c")
-        if c is not None and name in capi._INT_SIZES + capi._INT_SIZES2 + capi._INT_SIZES4 + ["meaninertia", "opt"]:
+        if c is not None and name in capi._INT_SIZES + capi._INT_SIZES2 + capi._INT_SIZES4 + capi._INT_SIZES6 + ["meaninertia", "opt"]:
             return getattr(c, name)
         raise AttributeError(name)
 
@@ -350,6 +350,39 @@ class Engine:
         o = self._ray_options(per_env, options)
         _chk(self.lib, self.lib.mjh_ray_device(self.h, env0, n, int(nray), C.c_void_p(d_pnt), C.c_void_p(d_vec), C.byref(o),
                                                C.c_void_p(d_dist), C.c_void_p(d_geomid)), "mjh_ray_device")
+
+    # ---- depth images (a camera of the model, every env)
+    def _depth_options(self, camera, width, height, options):
+        o = capi.DepthOptions()
+        self.lib.mjh_depth_default_options(C.byref(o))
+        if isinstance(camera, str):
+            cid = self.lib.mjh_name2id(self.model.ptr, 5, camera.encode())
+            if cid < 0:
+                raise ValueError(f"no camera named {camera!r}")
+            camera = cid
+        o.camera = int(camera); o.width = int(width); o.height = int(height)
+        for k, v in options.items():
+            if k not in ("bodyexclude", "flg_static", "range", "cull", "cutoff"):
+                raise TypeError(f"unknown depth option {k!r}")
+            setattr(o, k, v)
+        return o
+
+    def depth(self, camera, width, height, env0=0, n=None, **options):
+        """what camera `camera` (id or name) sees in envs [env0, env0 + n).  options: bodyexclude, flg_static, range, cull, cutoff
+        (mjh_depth_options).  -> (depth [n, height, width] float32, geomid [n, height, width] int32); a miss is (-1, -1)"""
+        n = self.nenv - env0 if n is None else n
+        o = self._depth_options(camera, width, height, options)
+        shape = (max(n, 0), max(o.height, 0), max(o.width, 0))
+        depth = np.zeros(shape, dtype=np.float32); gid = np.zeros(shape, dtype=np.int32)
+        _chk(self.lib, self.lib.mjh_depth(self.h, env0, n, C.byref(o), C.c_void_p(depth.ctypes.data), C.c_void_p(gid.ctypes.data)), "mjh_depth")
+        return depth, gid
+
+    def depth_device(self, d_depth, d_geomid, camera, width, height, env0=0, n=None, **options):
+        """mjh_depth_device: device addresses (data_ptr()) of fp32 depth and int32 geomid [n, height, width] (d_geomid may be None);
+        enqueued on the engine's stream, valid after synchronize()"""
+        n = self.nenv - env0 if n is None else n
+        o = self._depth_options(camera, width, height, options)
+        _chk(self.lib, self.lib.mjh_depth_device(self.h, env0, n, C.byref(o), C.c_void_p(d_depth), C.c_void_p(d_geomid)), "mjh_depth_device")
 
     def export_state_device(self, device_ptr):
         _chk(self.lib, self.lib.mjh_export_state_device(self.h, C.c_void_p(device_ptr)), "mjh_export_state_device")
