@@ -8,12 +8,12 @@
 
 #define RAW_STRIDE 7
 
-DEV void raw_emit(float* st, int k, float dist, const float* pos, const float* n) {
+HDEV void raw_emit(float* st, int k, float dist, const float* pos, const float* n) {
   float* o = st + k * RAW_STRIDE;
   o[0] = dist; o[1] = pos[0]; o[2] = pos[1]; o[3] = pos[2]; o[4] = n[0]; o[5] = n[1]; o[6] = n[2];
 }
 
-DEV int c_plane_sphere(const float* pp, const float* pm, const float* c, float r, float margin, float* st, int k) {
+HDEV int c_plane_sphere(const float* pp, const float* pm, const float* c, float r, float margin, float* st, int k) {
   float n[3] = {pm[2], pm[5], pm[8]}, t[3] = {c[0]-pp[0], c[1]-pp[1], c[2]-pp[2]};
   float dist = dot3(t, n) - r;
   if (dist > margin) return 0;
@@ -22,7 +22,7 @@ DEV int c_plane_sphere(const float* pp, const float* pm, const float* c, float r
   return 1;
 }
 
-DEV int c_plane_capsule(const float* pp, const float* pm, const float* c, const float* cm, const float* size, float margin, float* st) {
+HDEV int c_plane_capsule(const float* pp, const float* pm, const float* c, const float* cm, const float* size, float margin, float* st) {
   float ax[3] = {cm[2]*size[1], cm[5]*size[1], cm[8]*size[1]};
   float e1[3] = {c[0]+ax[0], c[1]+ax[1], c[2]+ax[2]}, e2[3] = {c[0]-ax[0], c[1]-ax[1], c[2]-ax[2]};
   int n = c_plane_sphere(pp, pm, e1, size[0], margin, st, 0);
@@ -32,7 +32,7 @@ DEV int c_plane_capsule(const float* pp, const float* pm, const float* c, const 
 
 // plane - cylinder: deepest rim point of the cap facing the plane, the same rim direction on the other cap, and two more
 // points of the near cap at +-120 degrees (a triangle under a standing cylinder); at most 4
-DEV int c_plane_cylinder(const float* pp, const float* pm, const float* c, const float* cm, const float* size, float margin, float* st) {
+HDEV int c_plane_cylinder(const float* pp, const float* pm, const float* c, const float* cm, const float* size, float margin, float* st) {
   const float n[3] = {pm[2], pm[5], pm[8]}, t[3] = {c[0]-pp[0], c[1]-pp[1], c[2]-pp[2]};
   float ax[3] = {cm[2], cm[5], cm[8]};
   const float r = size[0], h = size[1];
@@ -40,6 +40,9 @@ DEV int c_plane_cylinder(const float* pp, const float* pm, const float* c, const
   if (prjaxis > 0) { ax[0] = -ax[0]; ax[1] = -ax[1]; ax[2] = -ax[2]; prjaxis = -prjaxis; }   // axis points towards the plane
   const float dist0 = dot3(t, n);
   float vec[3] = {ax[0]*prjaxis - n[0], ax[1]*prjaxis - n[1], ax[2]*prjaxis - n[2]};          // -normal without its axial part
+  // (fp32: near standing the subtraction above leaves an axial remainder of rounding size, 6e-8, next to a vec of the tilt's size: scaled
+  //  to r it lifts the "rim" point off the cap by r 6e-8 / tilt, 5e-4 m at 1e-5 rad.  Taken out once more, vec lies in the cap's plane)
+  { const float rem = dot3(vec, ax); vec[0] -= ax[0]*rem; vec[1] -= ax[1]*rem; vec[2] -= ax[2]*rem; }
   const float len2 = dot3(vec, vec);
   if (len2 >= 1e-10f) { const float sc = r * rsqrtf(len2); vec[0] *= sc; vec[1] *= sc; vec[2] *= sc; }   // (threshold shared with the oracle)
   else { vec[0] = cm[0] * r; vec[1] = cm[3] * r; vec[2] = cm[6] * r; }                        // cap parallel to the plane: cylinder x axis
@@ -75,7 +78,7 @@ DEV int c_plane_cylinder(const float* pp, const float* pm, const float* c, const
 }
 
 // plane - ellipsoid: the support point of the ellipsoid against the plane normal
-DEV int c_plane_ellipsoid(const float* pp, const float* pm, const float* c, const float* em, const float* size, float margin, float* st) {
+HDEV int c_plane_ellipsoid(const float* pp, const float* pm, const float* c, const float* em, const float* size, float margin, float* st) {
   const float n[3] = {pm[2], pm[5], pm[8]}, nn[3] = {-n[0], -n[1], -n[2]};
   float dl[3], pl[3], pw[3];
   rotvecT(dl, em, nn);
@@ -95,7 +98,7 @@ DEV int c_plane_ellipsoid(const float* pp, const float* pm, const float* c, cons
 // plane - convex mesh: vertices below the margin; the deepest one, the one farthest from it, the one farthest from the
 // line through those two and the one farthest on the other side of that line; at most 4 (same definition as the oracle)
 #define PLANE_MESH_EPS2 1e-8f
-DEV int c_plane_mesh(const float* pp, const float* pm, const float* c, const float* mm, const float* vert, int nvert, float margin, float* st) {
+HDEV int c_plane_mesh(const float* pp, const float* pm, const float* c, const float* mm, const float* vert, int nvert, float margin, float* st) {
   const float n[3] = {pm[2], pm[5], pm[8]}, t[3] = {c[0]-pp[0], c[1]-pp[1], c[2]-pp[2]};
   float nl[3];
   rotvecT(nl, mm, n);
@@ -142,7 +145,7 @@ DEV int c_plane_mesh(const float* pp, const float* pm, const float* c, const flo
   return cnt;
 }
 
-DEV int c_plane_box(const float* pp, const float* pm, const float* c, const float* bm, const float* size, float margin, float* st) {
+HDEV int c_plane_box(const float* pp, const float* pm, const float* c, const float* bm, const float* size, float margin, float* st) {
   float n[3] = {pm[2], pm[5], pm[8]}, t[3] = {c[0]-pp[0], c[1]-pp[1], c[2]-pp[2]};
   float dist = dot3(t, n);
   int cnt = 0;
@@ -160,7 +163,7 @@ DEV int c_plane_box(const float* pp, const float* pm, const float* c, const floa
   return cnt;
 }
 
-DEV int c_sphere_sphere(const float* c1, float r1, const float* c2, float r2, float margin, float* st) {
+HDEV int c_sphere_sphere(const float* c1, float r1, const float* c2, float r2, float margin, float* st) {
   float t[3] = {c2[0]-c1[0], c2[1]-c1[1], c2[2]-c1[2]};
   float len = norm3(t), dist = len - r1 - r2;
   if (dist > margin) return 0;
@@ -170,14 +173,14 @@ DEV int c_sphere_sphere(const float* c1, float r1, const float* c2, float r2, fl
   return 1;
 }
 
-DEV int c_sphere_capsule(const float* c1, float r1, const float* c2, const float* m2, const float* s2, float margin, float* st) {
+HDEV int c_sphere_capsule(const float* c1, float r1, const float* c2, const float* m2, const float* s2, float margin, float* st) {
   float ax[3] = {m2[2], m2[5], m2[8]}, t[3] = {c1[0]-c2[0], c1[1]-c2[1], c1[2]-c2[2]};
   float x = fminf(s2[1], fmaxf(-s2[1], dot3(ax, t)));
   float p[3] = {c2[0] + ax[0]*x, c2[1] + ax[1]*x, c2[2] + ax[2]*x};
   return c_sphere_sphere(c1, r1, p, s2[0], margin, st);
 }
 
-DEV int c_capsule_capsule(const float* c1, const float* m1, const float* s1, const float* c2, const float* m2, const float* s2, float margin, float* st) {
+HDEV int c_capsule_capsule(const float* c1, const float* m1, const float* s1, const float* c2, const float* m2, const float* s2, float margin, float* st) {
   float a1[3] = {m1[2], m1[5], m1[8]}, a2[3] = {m2[2], m2[5], m2[8]}, dif[3] = {c1[0]-c2[0], c1[1]-c2[1], c1[2]-c2[2]};
   float ma = dot3(a1, a1), mb = -dot3(a1, a2), mc = dot3(a2, a2), u = -dot3(a1, dif), v = dot3(a2, dif);
   float det = ma * mc - mb * mb, x1, x2;
@@ -190,11 +193,30 @@ DEV int c_capsule_capsule(const float* c1, const float* m1, const float* s1, con
     x2 = fminf(s2[1], fmaxf(-s2[1], v / mc));
     x1 = fminf(s1[1], fmaxf(-s1[1], (u - mb * x2) / ma));
   }
+  // Near-parallel axes: in fp32 det is rounding noise (+-6e-8, or exactly 0) for axes closer than ~3e-4 rad, x1, x2 = noise / noise land
+  // anywhere inside their ranges, where no clamp repairs them, and the parallel branch is off by angle x length.  The minimum over
+  // the parameter box lies at the stationary point or on an edge, and the four edge minima need no det: the pair above is kept
+  // unless an edge's is closer by more than rounding (1e-5 of the squared distance; parallel axes keep the pair above).
+  {
+    auto sq = [&](const float y1, const float y2) __attribute__((always_inline)) {
+      const float w[3] = {dif[0] + a1[0]*y1 - a2[0]*y2, dif[1] + a1[1]*y1 - a2[1]*y2, dif[2] + a1[2]*y1 - a2[2]*y2};
+      return dot3(w, w); };
+    float best = sq(x1, x2);
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      const float sg = (e & 1) ? 1.0f : -1.0f;
+      float y1, y2;
+      if (e < 2) { y1 = sg * s1[1]; y2 = fminf(s2[1], fmaxf(-s2[1], (v - mb * y1) / mc)); }
+      else { y2 = sg * s2[1]; y1 = fminf(s1[1], fmaxf(-s1[1], (u - mb * y2) / ma)); }
+      const float d2 = sq(y1, y2);
+      if (d2 < best * (1.0f - 1e-5f)) { best = d2; x1 = y1; x2 = y2; }
+    }
+  }
   float p1[3] = {c1[0] + a1[0]*x1, c1[1] + a1[1]*x1, c1[2] + a1[2]*x1}, p2[3] = {c2[0] + a2[0]*x2, c2[1] + a2[1]*x2, c2[2] + a2[2]*x2};
   return c_sphere_sphere(p1, s1[0], p2, s2[0], margin, st);
 }
 
-DEV int c_sphere_box(const float* c1, float r1, const float* c2, const float* m2, const float* s2, float margin, float* st) {
+HDEV int c_sphere_box(const float* c1, float r1, const float* c2, const float* m2, const float* s2, float margin, float* st) {
   float t[3] = {c1[0]-c2[0], c1[1]-c2[1], c1[2]-c2[2]}, loc[3], cl[3];
   rotvecT(loc, m2, t);
   bool inside = true;

@@ -4,15 +4,19 @@
 #include <hip/hip_runtime.h>
 
 #define DEV __device__ __forceinline__
+#define HDEV __host__ __device__ __forceinline__   // the analytic pair routines and their helpers: also built for the host (tests/collide_host)
+#if !defined(__HIP_DEVICE_COMPILE__)
+static inline float rsqrtf(float x) { return 1.0f / sqrtf(x); }
+#endif
 #define MJ_MINVAL 1e-15f
 #define MJ_MAXVAL 1e10f
 
-DEV float dot3(const float* a, const float* b) { return a[0]*b[0] + a[1]*b[1] + a[2]*b[2]; }
-DEV void cross3(float* r, const float* a, const float* b) {
+HDEV float dot3(const float* a, const float* b) { return a[0]*b[0] + a[1]*b[1] + a[2]*b[2]; }
+HDEV void cross3(float* r, const float* a, const float* b) {
   float x = a[1]*b[2] - a[2]*b[1], y = a[2]*b[0] - a[0]*b[2], z = a[0]*b[1] - a[1]*b[0];
   r[0] = x; r[1] = y; r[2] = z;
 }
-DEV float norm3(const float* a) { return sqrtf(dot3(a, a)); }
+HDEV float norm3(const float* a) { return sqrtf(dot3(a, a)); }
 DEV float normalize3(float* a) {
   float n = norm3(a);
   if (n < MJ_MINVAL) { a[0] = 1; a[1] = 0; a[2] = 0; } else { float s = 1.0f / n; a[0] *= s; a[1] *= s; a[2] *= s; }
@@ -40,11 +44,11 @@ DEV void quat2mat(float* m, const float* q) {
   m[3] = 2*(x*y + w*z);         m[4] = w*w - x*x + y*y - z*z; m[5] = 2*(y*z - w*x);
   m[6] = 2*(x*z - w*y);         m[7] = 2*(y*z + w*x);         m[8] = w*w - x*x - y*y + z*z;
 }
-DEV void rotvec(float* r, const float* m, const float* v) {  // r = M v
+HDEV void rotvec(float* r, const float* m, const float* v) {  // r = M v
   float x = m[0]*v[0] + m[1]*v[1] + m[2]*v[2], y = m[3]*v[0] + m[4]*v[1] + m[5]*v[2], z = m[6]*v[0] + m[7]*v[1] + m[8]*v[2];
   r[0] = x; r[1] = y; r[2] = z;
 }
-DEV void rotvecT(float* r, const float* m, const float* v) {  // r = M^T v
+HDEV void rotvecT(float* r, const float* m, const float* v) {  // r = M^T v
   float x = m[0]*v[0] + m[3]*v[1] + m[6]*v[2], y = m[1]*v[0] + m[4]*v[1] + m[7]*v[2], z = m[2]*v[0] + m[5]*v[1] + m[8]*v[2];
   r[0] = x; r[1] = y; r[2] = z;
 }
@@ -202,7 +206,7 @@ DEV int wave_min_i(int v) {
 // Visits the vertices of a convex hull in index order, eight at a time: the loads of a batch are issued together (a plain loop
 // waits out the full memory latency per vertex — the hulls are read from global memory, a different one per lane).
 template <class F>
-DEV void mesh_scan(const float* vert, const int nvert, F f) {
+HDEV void mesh_scan(const float* vert, const int nvert, F f) {
   for (int i0 = 0; i0 < nvert; i0 += 8) {
     float x[8], y[8], z[8];
 #pragma unroll
