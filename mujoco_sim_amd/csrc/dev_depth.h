@@ -1,5 +1,5 @@
-// dev_depth.h — depth images (mjh_depth / mjh_depth_device): the launch descriptor shared by the host side (engine.hip) and the kernel
-// (depth.hip), the pixel-direction function and the sphere-cone predicate of the tile cull.  The two functions are __host__ __device__:
+// dev_depth.h — depth images (mjh_depth / mjh_depth_device): what the depth kernel (depth.hip) adds to the scene of dev_ray.h — its
+// launch descriptor, the pixel-direction function and the sphere-cone predicate of the tile cull.  The functions are __host__ __device__:
 // tests/depth_host builds them for the CPU and checks the very code the kernel runs.  gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -9,17 +9,10 @@
 #define DEPTH_TILE 8   // a wavefront renders a DEPTH_TILE x DEPTH_TILE pixel tile: column lane & 7, row lane >> 3
 
 struct DepthArgs {
-  const float *gpos, *gmat;        // geom poses of the n envs as the position stage exported them: [n][3 ngeom], [n][9 ngeom]
-  const float *xpos, *xquat;       // body poses [n][3 nbody], [n][4 nbody]
-  const float* size; long long size_stride;   // geom sizes: as RayArgs
-  const unsigned* slot_mask; int sbase;       // spawn / destroy slots: as RayArgs
-  const int4* ginfo;               // [ngeom]: the ray table of the engine's mesh mode (RayArgs::ginfo)
-  const RayHField* hf; const float* hf_data;
-  const RayMesh* mesh; const float4* planes;
+  RayScene W;
   float* depth; int* geomid;       // [n][height][width]; geomid may be null
-  int env0, n, width, height, ngeom, nbody;
-  int bodyexclude, flg_static, range, cull;
-  float cutoff;
+  int width, height;
+  int range, cull;                 // range: report the distance from the camera origin, not the depth; cull: the tile-cone test
   int cam_body; float cam_pos[3], cam_quat[4];   // camera frame in its body
   float scale;                     // tan(fovy / 2) / height: half the side of a (square) pixel on the plane z = -1
 };

@@ -1,5 +1,7 @@
-// dev_ray.h — batched ray casting (mj_ray semantics): the launch descriptor shared by the host side (engine.hip) and the kernel
-// (ray.hip), and the fp32 ray-geom intersections in the geom's own frame.  gfx950 only.
+// dev_ray.h — what the ray kernel (ray.hip) and the depth kernel (depth.hip) share: the scene descriptor the host side (engine.hip)
+// fills, the fp32 ray-geom intersections in the geom's own frame, and the code that takes a ray through an env's geoms — the frame
+// composition, the verdict on a geom, the staged record and the walk over the records.  All of it is __host__ __device__:
+// tests/ray_host builds it for the CPU and checks the very code the kernels run.  gfx950 only.
 //
 // Every intersection takes the ray origin p and direction v in the geom frame (v NOT normalised) and returns the smallest x >= 0 with
 // p + x v on the geom's surface, or -1.  Quadratics are solved about the point of closest approach (x = tc -+ sqrt(h2 / a) with
@@ -7,29 +9,36 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "../../include/mjhip.h"
+
 #define RAY_TILE 64   // rays per workgroup: one wavefront, one ray per lane
 #define RAY_PASS 64   // geom records one staging pass holds (one geom per lane)
-#define RAY_REC 20    // floats of a record: [0..2] world position, [3..11] rotation (row-major, world = R local), [12..14] the env's size,
-                      // [15] bounding radius, [16] type (int; -1: invisible in this env), [17] hfield id / mesh id (int), [18] geom id (int), [19] pad
+#define RAY_REC 20    // floats of a record (ray_store)
 
 struct RayHField { int nrow, ncol, adr, pad; float size[4]; };   // size: radius_x, radius_y, elevation_z, base_z
 
-struct RayMesh { int adr, num; float rbound, pad; };              // a mesh asset's planes [adr, adr + num) of RayArgs::planes; bounding radius of its vertices
+struct RayMesh { int adr, num; float rbound, pad; };              // a mesh asset's planes [adr, adr + num) of RayScene::planes; bounding radius of its vertices
 
-struct RayArgs {
-  const float *gpos, *gmat;        // geom poses of the n envs as the position stage exported them: [n][3 ngeom], [n][9 ngeom]
-  const float *xpos, *xquat;       // body poses [n][3 nbody], [n][4 nbody] (site >= 0 only)
+// what a kernel reads of the world: n envs from env0 on, as the position-stage launch exported them (engine.hip: ray_scene)
+struct RayScene {
+  const float *gpos, *gmat;        // geom poses of the n envs: [n][3 ngeom], [n][9 ngeom]
+  const float *xpos, *xquat;       // body poses [n][3 nbody], [n][4 nbody] (null unless asked for: a site's or a camera's body)
   const float* size; long long size_stride;   // geom sizes: row of env `e` at size + e * size_stride (per-env tables), or stride 0 (the shared model)
   const unsigned* slot_mask; int sbase;       // spawn / destroy slots: bit b of slot_mask[env] = body sbase + b is inactive (null: none)
   const int4* ginfo;               // [ngeom]: x type (-1: no ray sees it: hfield without an asset, mesh in mesh mode 0 or without planes), y body,
                                    // z 1 = static body, w hfield id / mesh id
   const RayHField* hf; const float* hf_data;
   const RayMesh* mesh; const float4* planes;   // mesh mode 1: [nmesh], [nmeshplane] (n.x, n.y, n.z, d: unit outward normal, inside is n.x <= d)
+  int env0, n, ngeom, nbody;
+  int bodyexclude, flg_static;     // the body no ray sees (-1: none); 0: no ray sees the geoms of static bodies
+  float cutoff;                    // > 0: a reported value beyond it is a miss
+};
+
+struct RayArgs {
+  RayScene W;
   const float *pnt, *vec;          // [nray][3], or [n][nray][3] with per_env
   float* dist; int* geomid;        // [n][nray]
-  int env0, n, nray, ngeom, nbody;
-  int per_env, bodyexclude, flg_static;
-  float cutoff;
+  int nray, per_env;
   int site_body; float site_pos[3], site_quat[4];   // site frame in its body (site_body < 0: rays are given in the world frame)
 };
 
@@ -250,5 +259,116 @@ RDEV float ray_hfield(const float* p, const float* v, const RayHField& H, const 
     }
   }
   return best;
+}
+
+// ---- a ray through the geoms of an env
+
+// a wave-uniform value read into a scalar register (the identity in a host compile)
+RDEV int ray_uniform(int x) {
+#ifdef __HIP_DEVICE_COMPILE__
+  return __builtin_amdgcn_readfirstlane(x);
+#else
+  return x;
+#endif
+}
+RDEV int ray_bits(float x) { return __builtin_bit_cast(int, x); }
+RDEV float ray_float(int x) { return __builtin_bit_cast(float, x); }
+
+// world origin o[3] and rotation S[9] (row-major, world = S local) of a frame (pos, quat) given in a body (a site, a camera), from the
+// body's exported world pose bp, bq.  A macro, not a function: the kernels' bits depend on it.  As an RDEV function (pos / quat as
+// pointers or as references to the descriptor's arrays alike) the same expressions compile to other bits, because the compiler orders
+// the operands of the quaternion product's sums differently and then fuses another product of a sum into the FMA (HISTORY.md).
+#define RAY_FRAME(bp, bq, pos, quat, o, S)                                                                                             \
+  do {                                                                                                                                 \
+    const float *const f_bp = (bp), *const f_bq = (bq), *const f_pos = (pos), *const f_quat = (quat);                                  \
+    const float w = f_bq[0], x = f_bq[1], y = f_bq[2], z = f_bq[3];                                                                    \
+    const float B[9] = {w*w + x*x - y*y - z*z, 2*(x*y - w*z), 2*(x*z + w*y), 2*(x*y + w*z), w*w - x*x + y*y - z*z, 2*(y*z - w*x),      \
+                        2*(x*z - w*y), 2*(y*z + w*x), w*w - x*x - y*y + z*z};                                                          \
+    const float a = f_quat[0], b = f_quat[1], c = f_quat[2], d = f_quat[3];                                                            \
+    const float sw = w*a - x*b - y*c - z*d, sx = w*b + x*a + y*d - z*c, sy = w*c - x*d + y*a + z*b, sz = w*d + x*c - y*b + z*a;        \
+    (S)[0] = sw*sw + sx*sx - sy*sy - sz*sz; (S)[1] = 2*(sx*sy - sw*sz); (S)[2] = 2*(sx*sz + sw*sy);                                    \
+    (S)[3] = 2*(sx*sy + sw*sz); (S)[4] = sw*sw - sx*sx + sy*sy - sz*sz; (S)[5] = 2*(sy*sz - sw*sx);                                    \
+    (S)[6] = 2*(sx*sz - sw*sy); (S)[7] = 2*(sy*sz + sw*sx); (S)[8] = sw*sw - sx*sx - sy*sy + sz*sz;                                    \
+    for (int k = 0; k < 3; k++) (o)[k] = f_bp[k] + B[3*k] * f_pos[0] + B[3*k+1] * f_pos[1] + B[3*k+2] * f_pos[2];                      \
+  } while (0)
+
+// the verdict on a geom (its ginfo row gi, its size s in the env, the env's slot mask): the type a ray sees, or -1 for a geom
+// invisible in this env; rb: the radius of its bounding sphere (of a mesh: of the model's mesh_vert — per-env sizes do not rescale a
+// mesh, in the narrow phase neither), a little larger than the geom's: the reject of the walk must never cost a hit
+RDEV int ray_verdict(const RayScene& W, const int4 gi, const float* s, unsigned slotmask, float& rb) {
+  rb = 0.0f;
+  if (gi.x == MJH_GEOM_SPHERE) rb = s[0];
+  else if (gi.x == MJH_GEOM_CAPSULE) rb = s[0] + s[1];
+  else if (gi.x == MJH_GEOM_ELLIPSOID) rb = fmaxf(s[0], fmaxf(s[1], s[2]));
+  else if (gi.x == MJH_GEOM_CYLINDER) rb = sqrtf(s[0]*s[0] + s[1]*s[1]);
+  else if (gi.x == MJH_GEOM_BOX) rb = sqrtf(s[0]*s[0] + s[1]*s[1] + s[2]*s[2]);
+  else if (gi.x == MJH_GEOM_MESH) rb = W.mesh[gi.w].rbound;
+  rb *= 1.001f;
+  const bool slot_off = gi.y >= W.sbase && gi.y - W.sbase < 32 && ((slotmask >> (gi.y - W.sbase)) & 1u);
+  const bool visible = gi.x >= 0 && gi.y != W.bodyexclude && (W.flg_static || !gi.z) && !slot_off;
+  return visible ? gi.x : -1;
+}
+
+// the record of a staged geom, RAY_REC floats: [0..2] world position, [3..11] rotation (row-major, world = R local), [12..14] the env's
+// size, [15] bounding radius, [16] type (int; -1: invisible in this env), [17] hfield id / mesh id (int), [18] geom id (int), [19] pad
+RDEV void ray_store(float* rec, const float* pos, const float* mat, const float* s, float rb, int type, int id, int g) {
+#pragma unroll
+  for (int k = 0; k < 3; k++) rec[k] = pos[k];
+#pragma unroll
+  for (int k = 0; k < 9; k++) rec[3 + k] = mat[k];
+#pragma unroll
+  for (int k = 0; k < 3; k++) rec[12 + k] = s[k];
+  rec[15] = rb;
+  rec[16] = ray_float(type);
+  rec[17] = ray_float(id);
+  rec[18] = ray_float(g);
+  rec[19] = 0.0f;
+}
+
+// the walk: the world-frame ray (p, v; vv = |v|^2; valid: 0 < vv < inf) against `cnt` staged records, in their order; best / bestg
+// keep the nearest hit, the earlier record on a tie.  In the kernels every lane of a wave walks the same records: the record index is
+// wave-uniform, so the type switch is a scalar branch and the record reads are LDS broadcasts.  SKIP: records of type -1 occur.
+template <bool SKIP>
+RDEV void ray_walk(const RayScene& W, const float* recs, int cnt, const float* p, const float* v, float vv, bool valid, float& best, int& bestg) {
+  for (int j = 0; j < cnt; j++) {
+    const float* rec = recs + j * RAY_REC;
+    const int type = ray_uniform(ray_bits(rec[16]));
+    if (SKIP && type < 0) continue;
+    // the ray in the geom's frame
+    const float d[3] = {p[0] - rec[0], p[1] - rec[1], p[2] - rec[2]};
+    const float lp[3] = {rec[3]*d[0] + rec[6]*d[1] + rec[9]*d[2], rec[4]*d[0] + rec[7]*d[1] + rec[10]*d[2], rec[5]*d[0] + rec[8]*d[1] + rec[11]*d[2]};
+    const float lv[3] = {rec[3]*v[0] + rec[6]*v[1] + rec[9]*v[2], rec[4]*v[0] + rec[7]*v[1] + rec[10]*v[2], rec[5]*v[0] + rec[8]*v[1] + rec[11]*v[2]};
+    const float sz[3] = {rec[12], rec[13], rec[14]};
+    float x = -1.0f;
+    if (type >= MJH_GEOM_SPHERE) {
+      // bounding-sphere reject: the origin outside the sphere and the ray pointing away from it, or passing it by
+      const float rb = rec[15];
+      const float b = lp[0]*lv[0] + lp[1]*lv[1] + lp[2]*lv[2], c = lp[0]*lp[0] + lp[1]*lp[1] + lp[2]*lp[2] - rb * rb;
+      const float tc = -b / vv;
+      const float q[3] = {lp[0] + tc * lv[0], lp[1] + tc * lv[1], lp[2] + tc * lv[2]};
+      const bool reject = !valid || (c > 0.0f && (b > 0.0f || q[0]*q[0] + q[1]*q[1] + q[2]*q[2] > rb * rb));
+      if (!reject) {
+        switch (type) {
+          case MJH_GEOM_SPHERE: x = ray_sphere(lp, lv, sz[0]); break;
+          case MJH_GEOM_CAPSULE: x = ray_capsule(lp, lv, sz); break;
+          case MJH_GEOM_ELLIPSOID: x = ray_ellipsoid(lp, lv, sz); break;
+          case MJH_GEOM_CYLINDER: x = ray_cylinder(lp, lv, sz); break;
+          case MJH_GEOM_BOX: x = ray_box(lp, lv, sz); break;
+          case MJH_GEOM_MESH: {      // the mesh id is wave-uniform: its table row and the planes come by scalar loads
+            const RayMesh Mh = W.mesh[ray_uniform(ray_bits(rec[17]))];
+            x = ray_convex(lp, lv, W.planes + Mh.adr, Mh.num);
+          } break;
+          default: break;
+        }
+      }
+    } else if (valid) {
+      if (type == MJH_GEOM_PLANE) x = ray_plane(lp, lv, sz);
+      else {
+        const RayHField H = W.hf[ray_uniform(ray_bits(rec[17]))];
+        x = ray_hfield(lp, lv, H, W.hf_data + H.adr);
+      }
+    }
+    if (x >= 0.0f && (bestg < 0 || x < best)) { best = x; bestg = ray_bits(rec[18]); }
+  }
 }
 #endif

@@ -1834,10 +1834,7 @@ extern "C" int mjh_debug_stop_at(mjh_engine* e, int stage, int with_inverse) {
   return launch(e, 0, e->nenv, 1, PH_STEP1 | PH_STEP2 | (with_inverse ? PH_INV : 0), stage << 8);
 }
 
-// ---- batched ray casting (mj_ray for every env: laser scans, range finders, terrain height under a foot).  The launch chain is the
-// position-stage launch of the env range (PH_FKONLY with XF_GEOM, plus XF_BODY for rays given in a site's frame) into the engine's
-// export scratch, exactly as fk_export issues it, then mjh_ray_kernel (ray.hip) on the same stream.  Nothing of the envs' state,
-// statistics or time is written.
+// ---- batched ray casting (mj_ray for every env: laser scans, range finders, terrain height under a foot) and depth images
 // what a ray can see of geom g in mesh mode 0: its type, or -1 (mesh geoms; an hfield geom without an asset)
 static int ray_geom_type(const mjh_model* m, int g) {
   const int t = m->geom_type[g];
@@ -1935,35 +1932,54 @@ static int ray_check(const mjh_engine* e, int env0, int n, int nray, const void*
   }
   return MJH_OK;
 }
+// The launch chain of mjh_ray_device and mjh_depth_device: the position-stage launch of the env range (PH_FKONLY with XF_GEOM, plus
+// XF_BODY when `bodies`: a site's or a camera's frame) into the engine's export scratch, exactly as fk_export issues it; the caller's
+// kernel follows on the same stream and reads what *W names.  Nothing of the envs' state, statistics or time is written.
+static int ray_scene(mjh_engine* e, int env0, int n, bool bodies, int bodyexclude, int flg_static, double cutoff, RayScene* W) {
+  int rc = ray_tables(e);
+  if (rc) return rc;
+  const int ng = e->M.ngeom, nb = e->M.nbody;
+  const size_t fg = (size_t)n * 3 * ng, fm = (size_t)n * 9 * ng, fx = bodies ? (size_t)n * 3 * nb : 0, fq = bodies ? (size_t)n * 4 * nb : 0;
+  rc = ensure_scratch(e, fg + fm + fx + fq);
+  if (rc) return rc;
+  W->gpos = e->scratch; W->gmat = e->scratch + fg;
+  W->xpos = bodies ? e->scratch + fg + fm : nullptr; W->xquat = bodies ? e->scratch + fg + fm + fx : nullptr;
+  {
+    StateGuard guard(&e->S);
+    e->S.x_gpos = e->scratch; e->S.x_gmat = e->scratch + fg;
+    if (bodies) { e->S.x_xpos = e->scratch + fg + fm; e->S.x_xquat = e->scratch + fg + fm + fx; }
+    rc = launch(e, env0, n, 1, PH_FKONLY, XF_GEOM | (bodies ? XF_BODY : 0));
+  }
+  if (rc) return rc;
+  if (e->S.p_geom_size) { W->size = e->S.p_geom_size; W->size_stride = e->S.p_stride; } else { W->size = e->dF + e->M.o_geom_size; W->size_stride = 0; }
+  W->slot_mask = e->S.slot_mask; W->sbase = nb > 32 ? nb - 32 : 0;
+  W->ginfo = e->ray_mesh_mode ? e->ray_ginfo_mesh : e->ray_ginfo; W->hf = e->ray_hf; W->hf_data = e->ray_hfdata;
+  W->mesh = e->ray_mesh; W->planes = e->ray_planes;
+  W->env0 = env0; W->n = n; W->ngeom = ng; W->nbody = nb;
+  W->bodyexclude = bodyexclude; W->flg_static = flg_static ? 1 : 0; W->cutoff = cutoff > 0 ? (float)cutoff : 0.0f;
+  return MJH_OK;
+}
+// the device staging buffer of mjh_ray and mjh_depth, grown to `need` floats
+static int ray_io_reserve(mjh_engine* e, size_t need) {
+  if (need <= e->ray_io_floats) return MJH_OK;
+  if (e->ray_io) { HIPCHK(hipStreamSynchronize(e->stream)); HIPCHK(hipFree(e->ray_io)); e->ray_io = nullptr; e->ray_io_floats = 0; }
+  HIPCHK(hipMalloc((void**)&e->ray_io, need * sizeof(float)));
+  e->ray_io_floats = need;
+  return MJH_OK;
+}
 extern "C" int mjh_ray_device(mjh_engine* e, int env0, int n, int nray, const float* d_pnt, const float* d_vec, const mjh_ray_options* opt,
                               float* d_dist, int* d_geomid) {
   ENG(e);
   int rc = ray_check(e, env0, n, nray, d_pnt, d_vec, opt, d_dist, d_geomid);
-  if (!rc) rc = ray_tables(e);
   if (rc) return rc;
   mjh_ray_options o; mjh_ray_default_options(&o);
   if (opt) o = *opt;
   const mjh_model* m = e->model;
-  const int ng = e->M.ngeom, nb = e->M.nbody;
-  const size_t fg = (size_t)n * 3 * ng, fm = (size_t)n * 9 * ng, fx = o.site >= 0 ? (size_t)n * 3 * nb : 0, fq = o.site >= 0 ? (size_t)n * 4 * nb : 0;
-  rc = ensure_scratch(e, fg + fm + fx + fq);
-  if (rc) return rc;
   RayArgs A{};
-  A.gpos = e->scratch; A.gmat = e->scratch + fg; A.xpos = e->scratch + fg + fm; A.xquat = e->scratch + fg + fm + fx;
-  {
-    StateGuard guard(&e->S);
-    e->S.x_gpos = e->scratch; e->S.x_gmat = e->scratch + fg;
-    if (o.site >= 0) { e->S.x_xpos = e->scratch + fg + fm; e->S.x_xquat = e->scratch + fg + fm + fx; }
-    rc = launch(e, env0, n, 1, PH_FKONLY, XF_GEOM | (o.site >= 0 ? XF_BODY : 0));
-  }
+  rc = ray_scene(e, env0, n, o.site >= 0, o.bodyexclude, o.flg_static, o.cutoff, &A.W);
   if (rc) return rc;
-  if (e->S.p_geom_size) { A.size = e->S.p_geom_size; A.size_stride = e->S.p_stride; } else { A.size = e->dF + e->M.o_geom_size; A.size_stride = 0; }
-  A.slot_mask = e->S.slot_mask; A.sbase = nb > 32 ? nb - 32 : 0;
-  A.ginfo = e->ray_mesh_mode ? e->ray_ginfo_mesh : e->ray_ginfo; A.hf = e->ray_hf; A.hf_data = e->ray_hfdata;
-  A.mesh = e->ray_mesh; A.planes = e->ray_planes;
   A.pnt = d_pnt; A.vec = d_vec; A.dist = d_dist; A.geomid = d_geomid;
-  A.env0 = env0; A.n = n; A.nray = nray; A.ngeom = ng; A.nbody = nb;
-  A.per_env = o.per_env ? 1 : 0; A.bodyexclude = o.bodyexclude; A.flg_static = o.flg_static ? 1 : 0; A.cutoff = o.cutoff > 0 ? (float)o.cutoff : 0.0f;
+  A.nray = nray; A.per_env = o.per_env ? 1 : 0;
   A.site_body = -1;
   if (o.site >= 0) {
     A.site_body = m->site_bodyid[o.site];
@@ -1984,12 +2000,8 @@ extern "C" int mjh_ray(mjh_engine* e, int env0, int n, int nray, const double* p
     if (vec[3*i] == 0.0 && vec[3*i+1] == 0.0 && vec[3*i+2] == 0.0) { mjh_set_error("mjh_ray: zero direction vector"); return MJH_ERR_ARG; }
     for (int k = 0; k < 3; k++) { h[3*i + k] = (float)pnt[3*i + k]; h[3*nin + 3*i + k] = (float)vec[3*i + k]; }
   }
-  const size_t need = 6 * nin + 2 * nout;
-  if (need > e->ray_io_floats) {
-    if (e->ray_io) { HIPCHK(hipStreamSynchronize(e->stream)); HIPCHK(hipFree(e->ray_io)); e->ray_io = nullptr; e->ray_io_floats = 0; }
-    HIPCHK(hipMalloc((void**)&e->ray_io, need * sizeof(float)));
-    e->ray_io_floats = need;
-  }
+  rc = ray_io_reserve(e, 6 * nin + 2 * nout);
+  if (rc) return rc;
   float* const d_in = e->ray_io; float* const d_dist = e->ray_io + 6 * nin; int* const d_gid = (int*)(e->ray_io + 6 * nin + nout);
   HIPCHK(hipMemcpyAsync(d_in, h.data(), 6 * nin * sizeof(float), hipMemcpyHostToDevice, e->stream));
   rc = mjh_ray_device(e, env0, n, nray, d_in, d_in + 3 * nin, opt, d_dist, d_gid);
@@ -2002,9 +2014,8 @@ extern "C" int mjh_ray(mjh_engine* e, int env0, int n, int nray, const double* p
   return MJH_OK;
 }
 
-// ---- depth images (mjh_depth / mjh_depth_device, depth.hip): the launch chain of mjh_ray_device with a site — the position-stage launch
-// of the env range (PH_FKONLY, XF_GEOM | XF_BODY) into the export scratch, then mjh_depth_kernel on the same stream.  The camera's world
-// pose is formed on the device from its body's exported pose; the tables are the ones ray_tables() uploads.
+// ---- depth images (mjh_depth / mjh_depth_device, depth.hip): ray_scene() with the body poses, then mjh_depth_kernel on the same stream.
+// The camera's world pose is formed on the device from its body's exported pose.
 extern "C" void mjh_depth_default_options(mjh_depth_options* o) {
   if (!o) return;
   o->camera = 0; o->width = 64; o->height = 64; o->bodyexclude = -1; o->flg_static = 1; o->range = 0; o->cull = 1; o->cutoff = 0.0;
@@ -2025,29 +2036,13 @@ extern "C" int mjh_depth_device(mjh_engine* e, int env0, int n, const mjh_depth_
   mjh_depth_options o; mjh_depth_default_options(&o);
   if (opt) o = *opt;
   int rc = depth_check(e, env0, n, o, d_depth);
-  if (!rc) rc = ray_tables(e);
   if (rc) return rc;
   const mjh_model* m = e->model;
-  const int ng = e->M.ngeom, nb = e->M.nbody;
-  const size_t fg = (size_t)n * 3 * ng, fm = (size_t)n * 9 * ng, fx = (size_t)n * 3 * nb, fq = (size_t)n * 4 * nb;
-  rc = ensure_scratch(e, fg + fm + fx + fq);
-  if (rc) return rc;
   DepthArgs A{};
-  A.gpos = e->scratch; A.gmat = e->scratch + fg; A.xpos = e->scratch + fg + fm; A.xquat = e->scratch + fg + fm + fx;
-  {
-    StateGuard guard(&e->S);
-    e->S.x_gpos = e->scratch; e->S.x_gmat = e->scratch + fg; e->S.x_xpos = e->scratch + fg + fm; e->S.x_xquat = e->scratch + fg + fm + fx;
-    rc = launch(e, env0, n, 1, PH_FKONLY, XF_GEOM | XF_BODY);
-  }
+  rc = ray_scene(e, env0, n, true, o.bodyexclude, o.flg_static, o.cutoff, &A.W);
   if (rc) return rc;
-  if (e->S.p_geom_size) { A.size = e->S.p_geom_size; A.size_stride = e->S.p_stride; } else { A.size = e->dF + e->M.o_geom_size; A.size_stride = 0; }
-  A.slot_mask = e->S.slot_mask; A.sbase = nb > 32 ? nb - 32 : 0;
-  A.ginfo = e->ray_mesh_mode ? e->ray_ginfo_mesh : e->ray_ginfo; A.hf = e->ray_hf; A.hf_data = e->ray_hfdata;
-  A.mesh = e->ray_mesh; A.planes = e->ray_planes;
   A.depth = d_depth; A.geomid = d_geomid;
-  A.env0 = env0; A.n = n; A.width = o.width; A.height = o.height; A.ngeom = ng; A.nbody = nb;
-  A.bodyexclude = o.bodyexclude; A.flg_static = o.flg_static ? 1 : 0; A.range = o.range ? 1 : 0; A.cull = o.cull ? 1 : 0;
-  A.cutoff = o.cutoff > 0 ? (float)o.cutoff : 0.0f;
+  A.width = o.width; A.height = o.height; A.range = o.range ? 1 : 0; A.cull = o.cull ? 1 : 0;
   A.cam_body = m->cam_bodyid[o.camera];
   for (int k = 0; k < 3; k++) A.cam_pos[k] = (float)m->cam_pos[3 * o.camera + k];
   for (int k = 0; k < 4; k++) A.cam_quat[k] = (float)m->cam_quat[4 * o.camera + k];
@@ -2061,12 +2056,9 @@ extern "C" int mjh_depth(mjh_engine* e, int env0, int n, const mjh_depth_options
   if (opt) o = *opt;
   int rc = depth_check(e, env0, n, o, depth);
   if (rc) return rc;
-  const size_t nout = (size_t)n * o.width * o.height, need = 2 * nout;      // the staging buffer of mjh_ray serves both
-  if (need > e->ray_io_floats) {
-    if (e->ray_io) { HIPCHK(hipStreamSynchronize(e->stream)); HIPCHK(hipFree(e->ray_io)); e->ray_io = nullptr; e->ray_io_floats = 0; }
-    HIPCHK(hipMalloc((void**)&e->ray_io, need * sizeof(float)));
-    e->ray_io_floats = need;
-  }
+  const size_t nout = (size_t)n * o.width * o.height;
+  rc = ray_io_reserve(e, 2 * nout);
+  if (rc) return rc;
   float* const d_depth = e->ray_io; int* const d_gid = (int*)(e->ray_io + nout);
   rc = mjh_depth_device(e, env0, n, &o, d_depth, geomid ? d_gid : nullptr);
   if (rc) return rc;

@@ -1,14 +1,17 @@
-// ray_host.hip — the ray kernel's own intersection code (csrc/dev_ray.h: __host__ __device__) evaluated on the CPU.
+// ray_host.hip — the ray and depth kernels' own code (csrc/dev_ray.h: __host__ __device__) evaluated on the CPU: the intersections,
+// and the frame composition, verdict, record and walk that take a ray through an env's geoms.
 //
 // Built two ways by tests/test_ray_host.py, never run on a GPU:
-//   * as a shared object: ray_host_cast() evaluates an array of geom-frame rays against one geom, for comparison with the fp64
-//     reference (tests/ray_ref.py);
+//   * as a shared object: ray_host_cast() evaluates an array of geom-frame rays against one geom and ray_host_scene() world-frame
+//     rays against a whole scene, for comparison with the fp64 references (tests/ray_ref.py, tests/ray_mesh_ref.py);
 //   * with -DRAY_HOST_MAIN and the host part under AddressSanitizer / UBSan as a stand-alone program: the memory-safety check of the
-//     cell walk's row / column clamping.  The elevation lives in an exactly-sized heap array, so a cell index one past the grid is
-//     an out-of-bounds read the sanitizer reports.
+//     cell walk's row / column clamping and of the scene cast.  The elevation, the staged records, ginfo and every table live in
+//     exactly-sized heap arrays, so a cell index one past the grid or a read past a record or a table is an out-of-bounds read
+//     the sanitizer reports.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -40,6 +43,57 @@ extern "C" void ray_host_cast(int type, const float* size, int nrow, int ncol, c
     }
     dist[i] = x;
   }
+}
+
+// World-frame rays through a whole scene of one env with the kernels' shared code (dev_ray.h: ray_verdict, ray_store, ray_walk): the
+// geoms are staged in passes of RAY_PASS, one record per geom as ray.hip does (an invisible geom's record has type -1 and the walk
+// skips it), or with `compact` only the visible geoms, in ascending id from record 0, as depth.hip does (its walk has no skip).  W.n is
+// 1: gpos / gmat are the env's; W.env0 selects the env's row of slot_mask and size.  dist / geomid [nray] as the kernels report them.
+extern "C" void ray_host_scene(const RayScene* Wp, int compact, int nray, const float* P, const float* V, float* dist, int* geomid) {
+  const RayScene& W = *Wp;
+  const unsigned slotmask = W.slot_mask ? W.slot_mask[W.env0] : 0u;
+  const float* const gsize = W.size + (size_t)W.env0 * (size_t)W.size_stride;
+  float* const recs = (float*)std::malloc(sizeof(float) * RAY_PASS * RAY_REC);      // exactly one pass: no slack behind it
+  for (int i = 0; i < nray; i++) { dist[i] = -1.0f; geomid[i] = -1; }
+  for (int base = 0; base < W.ngeom; base += RAY_PASS) {
+    int cnt = 0;
+    for (int lane = 0; lane < RAY_PASS && base + lane < W.ngeom; lane++) {
+      const int g = base + lane;
+      const int4 gi = W.ginfo[g];
+      float rb;
+      const int type = ray_verdict(W, gi, gsize + 3 * g, slotmask, rb);
+      if (compact && type < 0) continue;
+      ray_store(recs + (compact ? cnt : lane) * RAY_REC, W.gpos + 3 * g, W.gmat + 9 * g, gsize + 3 * g, rb, type, gi.w, g);
+      cnt = compact ? cnt + 1 : lane + 1;
+    }
+    for (int i = 0; i < nray; i++) {
+      const float* p = P + 3 * i;
+      const float* v = V + 3 * i;
+      const float vv = v[0]*v[0] + v[1]*v[1] + v[2]*v[2];
+      const bool valid = vv > 0.0f && vv < 3.0e38f;
+      if (compact) ray_walk<false>(W, recs, cnt, p, v, vv, valid, dist[i], geomid[i]);
+      else ray_walk<true>(W, recs, cnt, p, v, vv, valid, dist[i], geomid[i]);
+    }
+  }
+  for (int i = 0; i < nray; i++) {
+    if (W.cutoff > 0.0f && dist[i] > W.cutoff) geomid[i] = -1;
+    if (geomid[i] < 0) dist[i] = -1.0f;
+  }
+  std::free(recs);
+}
+
+// n frames given in bodies: body poses bp [n][3], bq [n][4], frames pos [n][3], quat [n][4] -> world origins o [n][3], rotations S [n][9]
+extern "C" void ray_host_frame(int n, const float* bp, const float* bq, const float* pos, const float* quat, float* o, float* S) {
+  for (int i = 0; i < n; i++) RAY_FRAME(bp + 3 * i, bq + 4 * i, pos + 3 * i, quat + 4 * i, o + 3 * i, S + 9 * i);
+}
+// the layout of RayScene for the test's ctypes mirror: the offset of every field in declaration order, then the size
+extern "C" void ray_host_scene_layout(int* out) {
+  const size_t off[] = {offsetof(RayScene, gpos), offsetof(RayScene, gmat), offsetof(RayScene, xpos), offsetof(RayScene, xquat), offsetof(RayScene, size),
+                        offsetof(RayScene, size_stride), offsetof(RayScene, slot_mask), offsetof(RayScene, sbase), offsetof(RayScene, ginfo), offsetof(RayScene, hf),
+                        offsetof(RayScene, hf_data), offsetof(RayScene, mesh), offsetof(RayScene, planes), offsetof(RayScene, env0), offsetof(RayScene, n),
+                        offsetof(RayScene, ngeom), offsetof(RayScene, nbody), offsetof(RayScene, bodyexclude), offsetof(RayScene, flg_static),
+                        offsetof(RayScene, cutoff), sizeof(RayScene)};
+  for (size_t k = 0; k < sizeof(off) / sizeof(off[0]); k++) out[k] = (int)off[k];
 }
 
 #ifdef RAY_HOST_MAIN
@@ -120,6 +174,64 @@ void run_primitives(uint64_t seed, long nray) {
       }
 }
 
+// the scene cast over heap arrays sized exactly to the scene: ngeom geoms of every type (nhf height fields of 3 x 4 nodes, nmesh
+// tetrahedra of 4 planes), some on an excluded body, some static, some in an inactive slot, some with a ginfo type of -1
+template <class T> T* exact(size_t n) { return (T*)std::malloc(sizeof(T) * (n ? n : 1)); }
+
+void run_scene(int ngeom, uint64_t seed, int nray) {
+  Rng R{seed};
+  const int nhf = 2, nmesh = 2, nbody = 40;
+  float *gpos = exact<float>(3 * (size_t)ngeom), *gmat = exact<float>(9 * (size_t)ngeom), *size = exact<float>(3 * (size_t)ngeom);
+  int4* gi = exact<int4>((size_t)ngeom);
+  unsigned* mask = exact<unsigned>(1);
+  RayHField* hf = exact<RayHField>(nhf);
+  float* hd = exact<float>(12 * nhf);
+  RayMesh* mesh = exact<RayMesh>(nmesh);
+  float4* planes = exact<float4>(4 * nmesh);
+  for (int h = 0; h < nhf; h++) {
+    hf[h].nrow = 3; hf[h].ncol = 4; hf[h].adr = 12 * h; hf[h].pad = 0;
+    hf[h].size[0] = 0.6f; hf[h].size[1] = 0.4f; hf[h].size[2] = 0.3f; hf[h].size[3] = 0.1f;
+    for (int k = 0; k < 12; k++) hd[12 * h + k] = R.uni(0.0f, 1.0f);
+  }
+  const float tn[4][3] = {{1, 1, 1}, {1, -1, -1}, {-1, 1, -1}, {-1, -1, 1}};
+  for (int m = 0; m < nmesh; m++) {
+    mesh[m].adr = 4 * m; mesh[m].num = 4; mesh[m].rbound = 0.3f * (float)(m + 1); mesh[m].pad = 0.0f;
+    for (int k = 0; k < 4; k++) planes[4 * m + k] = make_float4(tn[k][0] * 0.57735027f, tn[k][1] * 0.57735027f, tn[k][2] * 0.57735027f, 0.1f * (float)(m + 1));
+  }
+  mask[0] = 0x00010004u;      // bodies sbase + 2 and sbase + 16 are inactive
+  for (int g = 0; g < ngeom; g++) {
+    const float q[4] = {R.uni(-1, 1), R.uni(-1, 1), R.uni(-1, 1), R.uni(-1, 1)};
+    const float n = std::sqrt(q[0]*q[0] + q[1]*q[1] + q[2]*q[2] + q[3]*q[3]) + 1e-20f, w = q[0] / n, x = q[1] / n, y = q[2] / n, z = q[3] / n;
+    const float M[9] = {w*w + x*x - y*y - z*z, 2*(x*y - w*z), 2*(x*z + w*y), 2*(x*y + w*z), w*w - x*x + y*y - z*z, 2*(y*z - w*x), 2*(x*z - w*y), 2*(y*z + w*x), w*w - x*x - y*y + z*z};
+    for (int k = 0; k < 9; k++) gmat[9 * g + k] = M[k];
+    for (int k = 0; k < 3; k++) { gpos[3 * g + k] = R.uni(-2.0f, 2.0f); size[3 * g + k] = R.uni(0.1f, 0.4f); }
+    const int t = g % 9 == 8 ? -1 : g % 9;      // plane .. mesh in turn, then one no ray sees
+    gi[g] = make_int4(t, R.below(nbody), R.below(4) == 0, t == MJH_GEOM_HFIELD ? R.below(nhf) : t == MJH_GEOM_MESH ? R.below(nmesh) : -1);
+  }
+  float *P = exact<float>(3 * (size_t)nray), *V = exact<float>(3 * (size_t)nray), *dist = exact<float>((size_t)nray);
+  int* gid = exact<int>((size_t)nray);
+  for (int i = 0; i < nray; i++) {
+    const float t[3] = {R.uni(-2.0f, 2.0f), R.uni(-2.0f, 2.0f), R.uni(-2.0f, 2.0f)};
+    for (int k = 0; k < 3; k++) P[3 * i + k] = R.uni(-4.0f, 4.0f);
+    aim(R, P + 3 * i, t, V + 3 * i);
+  }
+  RayScene W{};
+  W.gpos = gpos; W.gmat = gmat; W.size = size; W.size_stride = 0; W.slot_mask = mask; W.sbase = nbody - 32; W.ginfo = gi;
+  W.hf = hf; W.hf_data = hd; W.mesh = mesh; W.planes = planes; W.env0 = 0; W.n = 1; W.ngeom = ngeom; W.nbody = nbody;
+  for (int mode = 0; mode < 4; mode++) {
+    W.bodyexclude = (mode & 1) ? 3 : -1; W.flg_static = (mode & 2) ? 0 : 1;
+    for (int compact = 0; compact < 2; compact++) {
+      ray_host_scene(&W, compact, nray, P, V, dist, gid);
+      for (int i = 0; i < nray; i++) {
+        tally(dist[i]);
+        if (gid[i] < -1 || gid[i] >= ngeom || (gid[i] < 0) != (dist[i] == -1.0f)) g_bad++;
+      }
+    }
+  }
+  std::free(gpos); std::free(gmat); std::free(size); std::free(gi); std::free(mask); std::free(hf); std::free(hd); std::free(mesh); std::free(planes);
+  std::free(P); std::free(V); std::free(dist); std::free(gid);
+}
+
 }  // namespace
 
 int main() {
@@ -129,6 +241,7 @@ int main() {
   run_terrain(17, 33, Cs, 63, 200000);
   run_terrain(2, 2, D, 64, 20000);       // the smallest grid: one cell
   run_primitives(65, 4000);
+  for (int ngeom : {1, 63, 64, 65, 130}) run_scene(ngeom, 66 + (uint64_t)ngeom, 2000);       // up to, at and past the pass boundary; a last partial pass
   std::printf("%ld rays, %ld hits, %ld failures\n", g_ray, g_hit, g_bad);
   return g_bad ? 1 : 0;
 }

@@ -27,11 +27,10 @@ import ray_ref as rr
 from helpers import D, set_opt
 from mujoco_sim_amd import capi
 from mujoco_sim_amd.engine import MjhError
+from ray_check import check
 
 pytestmark = pytest.mark.gpu
 
-TOL = 5e-5
-CAP = 0.02
 MJH_ERR_ARG = -1
 NENV = 4
 
@@ -100,28 +99,6 @@ def render(e, cam, width, height, **kw):
     assert d1.dtype == np.float32 and g1.dtype == np.int32 and d1.shape == g1.shape == (kw.get("n") or e.nenv - kw.get("env0", 0), height, width)
     assert np.array_equal(d1.view(np.uint32), d0.view(np.uint32)) and np.array_equal(g1, g0), "cull = 1 and cull = 0 give the same bits"
     return d1, g1
-
-
-def check(name, depth, gid, scene, rays, scale=None, cutoff=0.0):
-    """ONE env's image against the reference on the robust pixels; returns (largest scaled error, non-robust share)"""
-    depth = depth.reshape(-1).astype(float); gid = gid.reshape(-1)
-    ref_d, ref_g = rm.cast(rays[0], rays[1], scene)
-    if scale is not None:
-        ref_d = np.where(ref_g >= 0, ref_d * scale, ref_d)
-    if cutoff > 0:
-        far = ref_d > cutoff
-        ref_d = np.where(far, -1.0, ref_d); ref_g = np.where(far, -1, ref_g)
-    rob = rm.robust(rays, scene)
-    share = 1.0 - rob.mean()
-    hit = rob & (ref_g >= 0)
-    err = np.abs(depth - ref_d) / np.maximum(1.0, np.abs(ref_d))
-    worst = float(err[hit].max()) if hit.any() else 0.0
-    print(f"{name}: {len(rob)} pixels, non-robust share {share:.4f}, hits {int(hit.sum())}, max scaled error {worst:.3e}")
-    assert share <= CAP, name
-    assert (gid[rob] == ref_g[rob]).all(), name
-    assert (depth[rob & (ref_g < 0)] == -1.0).all() and (depth[gid < 0] == -1.0).all(), name
-    assert worst <= TOL, name
-    return worst, share
 
 
 # ------------------------------------------------------------------ models
