@@ -77,6 +77,7 @@ struct mjh_engine {
   // copies; the write side is a ring of slots, each fenced by an event, so mjh_set_cmd does not wait for the device
   float* h_io = nullptr; float* d_io = nullptr; hipEvent_t io_ev[MJH_IO_SLOTS] = {}; bool io_used[MJH_IO_SLOTS] = {}; unsigned io_next = 0;
   int win_lean = -1;        // (tests, MJH_WINDOW_LEAN read at creation: 1 / 0 forces the lean / the fat window instance of a model within 256 rows; -1: by the rows seen)
+  bool win_straight = true; // (MJH_WINDOW_STRAIGHT read at creation: 0 keeps the lean window instance in its general sweep loop; same values either way)
   int* h_wn = nullptr; int* d_wn = nullptr; int cur_cohort = -1;   // window models: largest row count per cohort (host-mapped, written by mjh_order_kernel); cohort of the launch being issued
   int* h_dense = nullptr; int* d_dense = nullptr; hipEvent_t ev_dense[MJH_MAX_COHORTS][4] = {}; unsigned dense_epoch[MJH_MAX_COHORTS] = {}; bool dense_now[MJH_MAX_COHORTS];
   int* dI = nullptr; float* dF = nullptr; DConst* dC = nullptr;
@@ -211,7 +212,7 @@ static int launch_on(mjh_engine* e, hipStream_t st, int env0, int n, int nsteps,
     // 24-dof models: a first section of wavefronts sweeps the envs with many rows in 32-row windows, two per wavefront (they scan the
     // same launch order and take the envs the assemble launch marked; almost all of them exit at once)
     const int n32 = (e->S.win32 && e->M.win_nvt == 24) ? (n + 1) / 2 : 0;
-    const int wxf = (xflags & ~XF_DEFER) | ((ph & PH_STEP1) ? 0 : XF_SPLIT2);
+    const int wxf = (xflags & ~XF_DEFER) | ((ph & PH_STEP1) ? 0 : XF_SPLIT2) | (e->win_straight ? XF_WSTRAIGHT : 0);
     const int n64 = (e->S.win64 && e->M.win_nvt == 24 && e->S.win64 < 16 * e->M.win_maxw) ? n : 0;      // the 64-row section: one wavefront per env of the launch order, almost all of them exit at once
     HIPCHK(mjh_launch_window(st, e->M.win_nvt, n64 + (e->M.win_nvt == 24 ? n32 : 0) + (n + 3) / 4, lds, e->dC, e->S, env0, n, nl, wxf, n32, n64));
   }
@@ -728,6 +729,7 @@ extern "C" int mjh_create(const mjh_model* m, int nenv, int device, void* stream
     rc |= dev_alloc(e, &S.wbuf, (size_t)nenv * (size_t)S.wstride, true);
   }
   if (const char* v = getenv("MJH_WINDOW_LEAN")) e->win_lean = atoi(v) != 0;
+  if (const char* v = getenv("MJH_WINDOW_STRAIGHT")) e->win_straight = atoi(v) != 0;
   if (M.window && e->lpt && nenv >= 1024) {
     HIPCHK(hipHostMalloc((void**)&e->h_wn, MJH_MAX_COHORTS * sizeof(int), hipHostMallocMapped));
     for (int g = 0; g < MJH_MAX_COHORTS; g++) e->h_wn[g] = 1 << 20;        // (nothing seen yet: keep the LDS tier)

@@ -419,11 +419,14 @@ DEV void wn_jt64(const float* J, const float x, float& a_lo, float& a_hi) {
   a_lo += s_lo; a_hi += s_hi;
 }
 // one 16-lane row's 16 constraint rows (lanes of DPP row mask m): per row  v_max, two wait states, v_fmac ... row_newbcast — the 16-row form's chain
-#define WN64_R4(r0, r1, r2, r3, a0_, a1_, a2_, a3_, m) asm volatile(WN_ROWM(r0, "%[a0]", m) WN_ROWM(r1, "%[a1]", m) WN_ROWM(r2, "%[a2]", m) WN_ROWM(r3, "%[a3]", m) \
-    : [t] "+v"(tt), [d] "=&v"(dl) : [nf] "v"(nf), [a0] "v"(a0_), [a1] "v"(a1_), [a2] "v"(a2_), [a3] "v"(a3_))
-#define WN64_CHAIN16(A, b, m) do { WN64_R4(0, 1, 2, 3, A[b], A[b + 1], A[b + 2], A[b + 3], m); WN64_R4(4, 5, 6, 7, A[b + 4], A[b + 5], A[b + 6], A[b + 7], m); \
-    WN64_R4(8, 9, 10, 11, A[b + 8], A[b + 9], A[b + 10], A[b + 11], m); WN64_R4(12, 13, 14, 15, A[b + 12], A[b + 13], A[b + 14], A[b + 15], m); \
-    asm volatile("v_max_f32 %0, %1, %2" : "=v"(dl) : "v"(tt), "v"(nf)); } while (0)
+// (ONE statement per chain, the closing v_max included: between two statements the compiler cannot see that `v_fmac ... dpp t` -> `v_max d, t` needs no
+//  wait state and puts an `s_nop 0` at every seam — three per chain and one in front of the closing v_max)
+#define WN64_CHAIN16(A, b, m) asm volatile( \
+    WN_ROWM(0, "%[a0]", m) WN_ROWM(1, "%[a1]", m) WN_ROWM(2, "%[a2]", m) WN_ROWM(3, "%[a3]", m) WN_ROWM(4, "%[a4]", m) WN_ROWM(5, "%[a5]", m) WN_ROWM(6, "%[a6]", m) WN_ROWM(7, "%[a7]", m) \
+    WN_ROWM(8, "%[a8]", m) WN_ROWM(9, "%[a9]", m) WN_ROWM(10, "%[a10]", m) WN_ROWM(11, "%[a11]", m) WN_ROWM(12, "%[a12]", m) WN_ROWM(13, "%[a13]", m) WN_ROWM(14, "%[a14]", m) WN_ROWM(15, "%[a15]", m) \
+    "v_max_f32 %[d], %[t], %[nf]" \
+    : [t] "+v"(tt), [d] "=&v"(dl) : [nf] "v"(nf), [a0] "v"(A[b]), [a1] "v"(A[b + 1]), [a2] "v"(A[b + 2]), [a3] "v"(A[b + 3]), [a4] "v"(A[b + 4]), [a5] "v"(A[b + 5]), [a6] "v"(A[b + 6]), [a7] "v"(A[b + 7]), \
+      [a8] "v"(A[b + 8]), [a9] "v"(A[b + 9]), [a10] "v"(A[b + 10]), [a11] "v"(A[b + 11]), [a12] "v"(A[b + 12]), [a13] "v"(A[b + 13]), [a14] "v"(A[b + 14]), [a15] "v"(A[b + 15]))
 // the deltas dx of a finished 16-lane row (replicated into every row) reach the rows behind it (mask m) through their cross entries
 #define WN64_XF(r, ar, m) "v_fmac_f32_dpp %[t], %[x], " ar " row_newbcast:" #r " row_mask:" #m " bank_mask:0xf\n\t"
 #define WN64_X4(r0, r1, r2, r3, a0_, a1_, a2_, a3_, m) asm volatile(WN64_XF(r0, "%[a0]", m) WN64_XF(r1, "%[a1]", m) WN64_XF(r2, "%[a2]", m) WN64_XF(r3, "%[a3]", m) \
@@ -471,15 +474,16 @@ DEV void wn_jt64(const float* J, const float x, float& a_lo, float& a_hi) {
 // of the wavefront run without nops; every lane still receives the rows' contributions in the same order (bitwise the sweep above).
 #define WN64_RF(r, ar, cr, m, mc) "v_max_f32 %[d], %[t], %[nf]\n\tv_fmac_f32_dpp %[t], %[xp], " cr " row_newbcast:" #r " row_mask:" #mc " bank_mask:0xf\n\t" \
                                   "v_fmac_f32_dpp %[t], %[d], " ar " row_newbcast:" #r " row_mask:" #m " bank_mask:0xf\n\t"
-#define WN64_R4F(r0, r1, r2, r3, a0_, a1_, a2_, a3_, c0_, c1_, c2_, c3_, m, mc, xp_) asm volatile( \
+// (two statements of eight rows: sixteen rows' tile and cross entries are more operands than one statement takes)
+#define WN64_R8F(r0, r1, r2, r3, r4, r5, r6, r7, A, b, bc, m, mc, xp_, tail) asm volatile( \
     WN64_RF(r0, "%[a0]", "%[c0]", m, mc) WN64_RF(r1, "%[a1]", "%[c1]", m, mc) WN64_RF(r2, "%[a2]", "%[c2]", m, mc) WN64_RF(r3, "%[a3]", "%[c3]", m, mc) \
-    : [t] "+v"(tt), [d] "=&v"(dl) : [nf] "v"(nf), [xp] "v"(xp_), [a0] "v"(a0_), [a1] "v"(a1_), [a2] "v"(a2_), [a3] "v"(a3_), [c0] "v"(c0_), [c1] "v"(c1_), [c2] "v"(c2_), [c3] "v"(c3_))
+    WN64_RF(r4, "%[a4]", "%[c4]", m, mc) WN64_RF(r5, "%[a5]", "%[c5]", m, mc) WN64_RF(r6, "%[a6]", "%[c6]", m, mc) WN64_RF(r7, "%[a7]", "%[c7]", m, mc) tail \
+    : [t] "+v"(tt), [d] "=&v"(dl) : [nf] "v"(nf), [xp] "v"(xp_), \
+      [a0] "v"(A[b + r0]), [a1] "v"(A[b + r1]), [a2] "v"(A[b + r2]), [a3] "v"(A[b + r3]), [a4] "v"(A[b + r4]), [a5] "v"(A[b + r5]), [a6] "v"(A[b + r6]), [a7] "v"(A[b + r7]), \
+      [c0] "v"(A[bc + r0]), [c1] "v"(A[bc + r1]), [c2] "v"(A[bc + r2]), [c3] "v"(A[bc + r3]), [c4] "v"(A[bc + r4]), [c5] "v"(A[bc + r5]), [c6] "v"(A[bc + r6]), [c7] "v"(A[bc + r7]))
 #define WN64_CHAIN16F(A, b, m, bc, mc, xp_) do { \
-    WN64_R4F(0, 1, 2, 3, A[b], A[b + 1], A[b + 2], A[b + 3], A[bc], A[bc + 1], A[bc + 2], A[bc + 3], m, mc, xp_); \
-    WN64_R4F(4, 5, 6, 7, A[b + 4], A[b + 5], A[b + 6], A[b + 7], A[bc + 4], A[bc + 5], A[bc + 6], A[bc + 7], m, mc, xp_); \
-    WN64_R4F(8, 9, 10, 11, A[b + 8], A[b + 9], A[b + 10], A[b + 11], A[bc + 8], A[bc + 9], A[bc + 10], A[bc + 11], m, mc, xp_); \
-    WN64_R4F(12, 13, 14, 15, A[b + 12], A[b + 13], A[b + 14], A[b + 15], A[bc + 12], A[bc + 13], A[bc + 14], A[bc + 15], m, mc, xp_); \
-    asm volatile("v_max_f32 %0, %1, %2" : "=v"(dl) : "v"(tt), "v"(nf)); } while (0)
+    WN64_R8F(0, 1, 2, 3, 4, 5, 6, 7, A, b, bc, m, mc, xp_, ""); \
+    WN64_R8F(8, 9, 10, 11, 12, 13, 14, 15, A, b, bc, m, mc, xp_, "v_max_f32 %[d], %[t], %[nf]"); } while (0)
 #define WN64_SWEEP_F(W, fw) do { \
     const float u = wn_dot<NV>(W.J, a_lo, a_hi); \
     const float fo = fw; \
@@ -700,21 +704,38 @@ template <int NV> DEV void wn_jt2(const float* JA, const float xa, const float* 
 #endif
 #define WN_ROWF(r, ar, fill) "v_max_f32 %[d], %[t], %[nf]\n\t" fill "\n\tv_fmac_f32_dpp %[t], %[d], " ar " row_newbcast:" #r " row_mask:0xf bank_mask:0xf\n\t"
 #define WN_FDOT(r, jb) "v_fmac_f32_dpp %[ub], %[al], " jb " row_newbcast:" #r " row_mask:0xf bank_mask:0xf"
-// window A's rows r0 .. r0 + 3 (tile entries a0 .. a3), filler: window B's dot over dofs r0 .. r0 + 3 (b0 .. b3 = B.J[r0 ..])
-#define WN_ROWS4_FA(r0, r1, r2, r3, T, b0_, b1_, b2_, b3_) asm volatile( \
-    WN_ROWF(r0, "%[a0]", WN_FDOT(r0, "%[b0]")) WN_ROWF(r1, "%[a1]", WN_FDOT(r1, "%[b1]")) WN_ROWF(r2, "%[a2]", WN_FDOT(r2, "%[b2]")) WN_ROWF(r3, "%[a3]", WN_FDOT(r3, "%[b3]")) \
-    : [t] "+v"(tt), [d] "=&v"(dl), [ub] "+v"(ub0) : [nf] "v"(nf), [a0] "v"(T.x), [a1] "v"(T.y), [a2] "v"(T.z), [a3] "v"(T.w), [al] "v"(a_lo), [b0] "v"(b0_), [b1] "v"(b1_), [b2] "v"(b2_), [b3] "v"(b3_))
-// window B's rows, filler: window A's products p_k = J^_A[2k .. 2k + 1] * delta_A (packed)
+// Eight rows to a statement, the chain's closing v_max in its last one: between two statements the compiler cannot see that `v_fmac ... dpp t` ->
+// `v_max d, t` needs no wait state and puts an `s_nop 0` at every seam (four per chain with one statement per four rows; sixteen rows with their
+// fillers are more operands than one statement takes).
+// window A's rows 0 .. 7 (T0, T1: their tile entries), filler: window B's dot over dofs 0 .. 7 (row 0's opens it: a product, not a multiply-add)
+#define WN_ROWS8_FA0(T0, T1, BJ) asm volatile( \
+    WN_ROWF(0, "%[a0]", "v_mul_f32_dpp %[ub], %[al], %[b0] row_newbcast:0 row_mask:0xf bank_mask:0xf") WN_ROWF(1, "%[a1]", WN_FDOT(1, "%[b1]")) WN_ROWF(2, "%[a2]", WN_FDOT(2, "%[b2]")) WN_ROWF(3, "%[a3]", WN_FDOT(3, "%[b3]")) \
+    WN_ROWF(4, "%[a4]", WN_FDOT(4, "%[b4]")) WN_ROWF(5, "%[a5]", WN_FDOT(5, "%[b5]")) WN_ROWF(6, "%[a6]", WN_FDOT(6, "%[b6]")) WN_ROWF(7, "%[a7]", WN_FDOT(7, "%[b7]")) \
+    : [t] "+v"(tt), [d] "=&v"(dl), [ub] "=&v"(ub0) : [nf] "v"(nf), [al] "v"(a_lo), [a0] "v"(T0.x), [a1] "v"(T0.y), [a2] "v"(T0.z), [a3] "v"(T0.w), [a4] "v"(T1.x), [a5] "v"(T1.y), [a6] "v"(T1.z), [a7] "v"(T1.w), \
+      [b0] "v"(BJ[0]), [b1] "v"(BJ[1]), [b2] "v"(BJ[2]), [b3] "v"(BJ[3]), [b4] "v"(BJ[4]), [b5] "v"(BJ[5]), [b6] "v"(BJ[6]), [b7] "v"(BJ[7]))
+// ... rows 8 .. 15, filler: dofs 8 .. 15 of that dot
+#define WN_ROWS8_FA1(T0, T1, BJ) asm volatile( \
+    WN_ROWF(8, "%[a0]", WN_FDOT(8, "%[b0]")) WN_ROWF(9, "%[a1]", WN_FDOT(9, "%[b1]")) WN_ROWF(10, "%[a2]", WN_FDOT(10, "%[b2]")) WN_ROWF(11, "%[a3]", WN_FDOT(11, "%[b3]")) \
+    WN_ROWF(12, "%[a4]", WN_FDOT(12, "%[b4]")) WN_ROWF(13, "%[a5]", WN_FDOT(13, "%[b5]")) WN_ROWF(14, "%[a6]", WN_FDOT(14, "%[b6]")) WN_ROWF(15, "%[a7]", WN_FDOT(15, "%[b7]")) \
+    "v_max_f32 %[d], %[t], %[nf]" \
+    : [t] "+v"(tt), [d] "=&v"(dl), [ub] "+v"(ub0) : [nf] "v"(nf), [al] "v"(a_lo), [a0] "v"(T0.x), [a1] "v"(T0.y), [a2] "v"(T0.z), [a3] "v"(T0.w), [a4] "v"(T1.x), [a5] "v"(T1.y), [a6] "v"(T1.z), [a7] "v"(T1.w), \
+      [b0] "v"(BJ[8]), [b1] "v"(BJ[9]), [b2] "v"(BJ[10]), [b3] "v"(BJ[11]), [b4] "v"(BJ[12]), [b5] "v"(BJ[13]), [b6] "v"(BJ[14]), [b7] "v"(BJ[15]))
+// window B's rows 0 .. 7, filler: window A's products p_k = J^_A[2k .. 2k + 1] * delta_A (packed), k = 0 .. 7
 #define WN_FPK(pk, ja) "v_pk_mul_f32 " pk ", " ja ", %[x2]"
-#define WN_ROWS4_FB(r0, r1, r2, r3, T, p0_, p1_, p2_, p3_, j0_, j1_, j2_, j3_) asm volatile( \
-    WN_ROWF(r0, "%[a0]", WN_FPK("%[p0]", "%[j0]")) WN_ROWF(r1, "%[a1]", WN_FPK("%[p1]", "%[j1]")) WN_ROWF(r2, "%[a2]", WN_FPK("%[p2]", "%[j2]")) WN_ROWF(r3, "%[a3]", WN_FPK("%[p3]", "%[j3]")) \
-    : [t] "+v"(tt), [d] "=&v"(dl), [p0] "=&v"(p0_), [p1] "=&v"(p1_), [p2] "=&v"(p2_), [p3] "=&v"(p3_) \
-    : [nf] "v"(nf), [a0] "v"(T.x), [a1] "v"(T.y), [a2] "v"(T.z), [a3] "v"(T.w), [x2] "v"(xa2), [j0] "v"(j0_), [j1] "v"(j1_), [j2] "v"(j2_), [j3] "v"(j3_))
-// ... and the float part of A's cost decrease: e = ((half_A delta_A) (2 t_A - delta_A)) qs
-#define WN_ROWS4_FC(r0, r1, r2, r3, T) asm volatile( \
-    WN_ROWF(r0, "%[a0]", "v_mul_f32 %[e1], %[hf], %[da]") WN_ROWF(r1, "%[a1]", "v_fma_f32 %[e2], 2.0, %[ta], -%[da]") WN_ROWF(r2, "%[a2]", "v_mul_f32 %[e1], %[e1], %[e2]") WN_ROWF(r3, "%[a3]", "v_mul_f32 %[e1], %[e1], %[qs]") \
-    : [t] "+v"(tt), [d] "=&v"(dl), [e1] "=&v"(e1), [e2] "=&v"(e2) \
-    : [nf] "v"(nf), [a0] "v"(T.x), [a1] "v"(T.y), [a2] "v"(T.z), [a3] "v"(T.w), [hf] "v"(A.half), [da] "v"(dla), [ta] "v"(tta), [qs] "v"(iq.qs))
+#define WN_ROWS8_FB0(T0, T1, P, JA) asm volatile( \
+    WN_ROWF(0, "%[a0]", WN_FPK("%[p0]", "%[j0]")) WN_ROWF(1, "%[a1]", WN_FPK("%[p1]", "%[j1]")) WN_ROWF(2, "%[a2]", WN_FPK("%[p2]", "%[j2]")) WN_ROWF(3, "%[a3]", WN_FPK("%[p3]", "%[j3]")) \
+    WN_ROWF(4, "%[a4]", WN_FPK("%[p4]", "%[j4]")) WN_ROWF(5, "%[a5]", WN_FPK("%[p5]", "%[j5]")) WN_ROWF(6, "%[a6]", WN_FPK("%[p6]", "%[j6]")) WN_ROWF(7, "%[a7]", WN_FPK("%[p7]", "%[j7]")) \
+    : [t] "+v"(tt), [d] "=&v"(dl), [p0] "=&v"(P[0]), [p1] "=&v"(P[1]), [p2] "=&v"(P[2]), [p3] "=&v"(P[3]), [p4] "=&v"(P[4]), [p5] "=&v"(P[5]), [p6] "=&v"(P[6]), [p7] "=&v"(P[7]) \
+    : [nf] "v"(nf), [x2] "v"(xa2), [a0] "v"(T0.x), [a1] "v"(T0.y), [a2] "v"(T0.z), [a3] "v"(T0.w), [a4] "v"(T1.x), [a5] "v"(T1.y), [a6] "v"(T1.z), [a7] "v"(T1.w), \
+      [j0] "v"(WN_J2(JA, 0)), [j1] "v"(WN_J2(JA, 1)), [j2] "v"(WN_J2(JA, 2)), [j3] "v"(WN_J2(JA, 3)), [j4] "v"(WN_J2(JA, 4)), [j5] "v"(WN_J2(JA, 5)), [j6] "v"(WN_J2(JA, 6)), [j7] "v"(WN_J2(JA, 7)))
+// ... rows 8 .. 11 with the products k = 8 .. 11, rows 12 .. 15 with the float part of A's cost decrease: e = ((half_A delta_A) (2 t_A - delta_A)) qs
+#define WN_ROWS8_FB1(T0, T1, P, JA) asm volatile( \
+    WN_ROWF(8, "%[a0]", WN_FPK("%[p0]", "%[j0]")) WN_ROWF(9, "%[a1]", WN_FPK("%[p1]", "%[j1]")) WN_ROWF(10, "%[a2]", WN_FPK("%[p2]", "%[j2]")) WN_ROWF(11, "%[a3]", WN_FPK("%[p3]", "%[j3]")) \
+    WN_ROWF(12, "%[a4]", "v_mul_f32 %[e1], %[hf], %[da]") WN_ROWF(13, "%[a5]", "v_fma_f32 %[e2], 2.0, %[ta], -%[da]") WN_ROWF(14, "%[a6]", "v_mul_f32 %[e1], %[e1], %[e2]") WN_ROWF(15, "%[a7]", "v_mul_f32 %[e1], %[e1], %[qs]") \
+    "v_max_f32 %[d], %[t], %[nf]" \
+    : [t] "+v"(tt), [d] "=&v"(dl), [p0] "=&v"(P[8]), [p1] "=&v"(P[9]), [p2] "=&v"(P[10]), [p3] "=&v"(P[11]), [e1] "=&v"(e1), [e2] "=&v"(e2) \
+    : [nf] "v"(nf), [x2] "v"(xa2), [a0] "v"(T0.x), [a1] "v"(T0.y), [a2] "v"(T0.z), [a3] "v"(T0.w), [a4] "v"(T1.x), [a5] "v"(T1.y), [a6] "v"(T1.z), [a7] "v"(T1.w), \
+      [j0] "v"(WN_J2(JA, 8)), [j1] "v"(WN_J2(JA, 9)), [j2] "v"(WN_J2(JA, 10)), [j3] "v"(WN_J2(JA, 11)), [hf] "v"(A.half), [da] "v"(dla), [ta] "v"(tta), [qs] "v"(iq.qs))
 
 // Cross tiles of the register-resident pairs in LDS instead of registers (the 24-slot instance): 16 values per pair and lane that the sweep uses once,
 // in four `ds_read_b128` instead of sixteen copies out of the accumulation half of the register file (a VALU instruction takes its operands from
@@ -725,6 +746,9 @@ template <int NV> DEV void wn_jt2(const float* JA, const float xa, const float* 
 #endif
 // Only launches WITHOUT the LDS tier take it (instance XL; S24's default): beside the tier's 36 KB the 12 KB would cost the fourth window wavefront
 // of a CU its place (S24D: 5.83 -> 4.67 M, measured).
+#ifndef WN_STRAIGHT
+#define WN_STRAIGHT 1      // (0: builds without the straight-line sweep loops of the lean instance)
+#endif
 #define WN_XLDS_BYTES(nvt, nw) (((nvt) == 24 && WN_FILL && WN_X_LDS) ? ((nw) / 2) * 4 * 64 * 16 : 0)
 // N64W / N64T: 64-row windows of the 64-row section that are register-resident / that keep their tiles in LDS.  Launches with the LDS tier
 // (and every launch of a model whose rows can exceed 256) run <.., WN64_NW, WN64_NT>; launches without it — instance XL, models within 256 rows:
@@ -931,11 +955,7 @@ __global__ __launch_bounds__(64, 1) void mjh_window_kernel(const DConst* __restr
         float tt = ((ua - A.aref) + A.R * foa) * A.nw;
         const float nf = -foa;
         float dl;
-        // (row 0's filler opens window B's dot: a product, not a multiply-add)
-        asm volatile(WN_ROWF(0, "%[a0]", "v_mul_f32_dpp %[ub], %[al], %[b0] row_newbcast:0 row_mask:0xf bank_mask:0xf") WN_ROWF(1, "%[a1]", WN_FDOT(1, "%[b1]")) WN_ROWF(2, "%[a2]", WN_FDOT(2, "%[b2]")) WN_ROWF(3, "%[a3]", WN_FDOT(3, "%[b3]"))
-                     : [t] "+v"(tt), [d] "=&v"(dl), [ub] "=&v"(ub0) : [nf] "v"(nf), [a0] "v"(A.A0.x), [a1] "v"(A.A0.y), [a2] "v"(A.A0.z), [a3] "v"(A.A0.w), [al] "v"(a_lo), [b0] "v"(B.J[0]), [b1] "v"(B.J[1]), [b2] "v"(B.J[2]), [b3] "v"(B.J[3]));
-        WN_ROWS4_FA(4, 5, 6, 7, A.A1, B.J[4], B.J[5], B.J[6], B.J[7]); WN_ROWS4_FA(8, 9, 10, 11, A.A2, B.J[8], B.J[9], B.J[10], B.J[11]); WN_ROWS4_FA(12, 13, 14, 15, A.A3, B.J[12], B.J[13], B.J[14], B.J[15]);
-        asm volatile("v_max_f32 %0, %1, %2" : "=v"(dl) : "v"(tt), "v"(nf));
+        WN_ROWS8_FA0(A.A0, A.A1, B.J); WN_ROWS8_FA1(A.A2, A.A3, B.J);
         fa = foa + dl; dla = dl; tta = tt;
       }
       v2f p[NV / 2];
@@ -949,12 +969,8 @@ __global__ __launch_bounds__(64, 1) void mjh_window_kernel(const DConst* __restr
         const float nf = -fob;
         float dl;
         const v2f xa2 = {dla, dla};
-#define WN_J2(W, k) v2f{W.J[2 * (k)], W.J[2 * (k) + 1]}
-        WN_ROWS4_FB(0, 1, 2, 3, B.A0, p[0], p[1], p[2], p[3], WN_J2(A, 0), WN_J2(A, 1), WN_J2(A, 2), WN_J2(A, 3));
-        WN_ROWS4_FB(4, 5, 6, 7, B.A1, p[4], p[5], p[6], p[7], WN_J2(A, 4), WN_J2(A, 5), WN_J2(A, 6), WN_J2(A, 7));
-        WN_ROWS4_FB(8, 9, 10, 11, B.A2, p[8], p[9], p[10], p[11], WN_J2(A, 8), WN_J2(A, 9), WN_J2(A, 10), WN_J2(A, 11));
-        WN_ROWS4_FC(12, 13, 14, 15, B.A3);
-        asm volatile("v_max_f32 %0, %1, %2" : "=v"(dl) : "v"(tt), "v"(nf));
+#define WN_J2(J, k) v2f{J[2 * (k)], J[2 * (k) + 1]}
+        WN_ROWS8_FB0(B.A0, B.A1, p, A.J); WN_ROWS8_FB1(B.A2, B.A3, p, A.J);
         impl += (int)__builtin_amdgcn_fmed3f(e1, -(float)(2 << MJH_IMP_BITS), (float)(2 << MJH_IMP_BITS));
         impl += imp_fixed((B.half * dl) * (2.0f * tt - dl), iq.qs);
         fb = fob + dl; dlb = dl;
@@ -963,28 +979,64 @@ __global__ __launch_bounds__(64, 1) void mjh_window_kernel(const DConst* __restr
         const v2f xb2 = {dlb, dlb};
         float pp[NV];
 #pragma unroll
-        for (int k = 0; k < NV / 2; k++) { const v2f pr = __builtin_elementwise_fma(WN_J2(B, k), xb2, p[k]); pp[2 * k] = pr.x; pp[2 * k + 1] = pr.y; }
+        for (int k = 0; k < NV / 2; k++) { const v2f pr = __builtin_elementwise_fma(WN_J2(B.J, k), xb2, p[k]); pp[2 * k] = pr.x; pp[2 * k + 1] = pr.y; }
 #undef WN_J2
         a_lo += wn_fold16(pp);
         a_hi += wn_fold8(pp + 16);
       }
     }
   };
+#define WN_SWEEP_ONE(W, fw) do { \
+    const float u = wn_dot<NV>(W.J, a_lo, a_hi); \
+    const float fo = fw; \
+    float tt = ((u - W.aref) + W.R * fo) * W.nw; \
+    const float nf = -fo; \
+    float dl; \
+    PP_ROWS4(0, 1, 2, 3, W.A0); PP_ROWS4(4, 5, 6, 7, W.A1); PP_ROWS4(8, 9, 10, 11, W.A2); PP_ROWS4(12, 13, 14, 15, W.A3); \
+    asm volatile("v_max_f32 %0, %1, %2" : "=v"(dl) : "v"(tt), "v"(nf)); \
+    impl += imp_fixed((W.half * dl) * (2.0f * tt - dl), iq.qs); \
+    fw = fo + dl; \
+    wn_jt<NV>(W.J, dl, a_lo, a_hi); } while (0)
   bool act = nrow > 0;
+  // Launches without the tiers (instance XL) whose wavefront keeps every window in registers — all of S24's, with the 64-row section on —
+  // sweep in a loop that is straight-line for the wavefront's number of window PAIRS (wave-uniform: one body per 1, 2, 3 pairs, the last
+  // pair or a last odd window under one uniform branch): no tier loops, no tier pointers, no `w < nwmax` tests in the sweep.  Same
+  // instructions on the same values in the same order as the general loop below, which stays for every other wavefront
+  // (XF_WSTRAIGHT: engine.hip, MJH_WINDOW_STRAIGHT).
+  // The two __builtin_expect are part of the register budget (tests/test_window_register_budget.py): with both loops weighed alike the
+  // allocator takes 385 registers for the instance, with the general loop marked cold 373 (the straight loops alone: 360).
+  bool swept = false;
+  if constexpr (X_LDS && WN_STRAIGHT) {
+    if (__builtin_expect((xflags & XF_WSTRAIGHT) && nwmax <= NW, 1)) {
+      auto sweeps_straight = [&](auto npair) __attribute__((always_inline)) {
+        constexpr int NP = decltype(npair)::value;
+        const bool odd = (nwmax & 1) != 0;
+        while (__ballot(act) != 0ull) {
+          if (act) {
+            impl = 0;
+#pragma unroll
+            for (int j = 0; j < NP; j++) {
+              if (j == NP - 1 && odd) { WnWin<NV>& W = win[2 * j]; WN_SWEEP_ONE(W, f[2 * j]); }
+              else {
+                const float4 x0 = xs[(4 * j) * 64], x1 = xs[(4 * j + 1) * 64], x2 = xs[(4 * j + 2) * 64], x3 = xs[(4 * j + 3) * 64];
+                sweep_pair_fill(win[2 * j], win[2 * j + 1], x0, x1, x2, x3, f[2 * j], f[2 * j + 1]);
+              }
+            }
+            niter++;
+            if (wn_rowsum_i(impl) < iq.thr || niter >= itmax) act = false;
+          }
+        }
+      };
+      if (nwmax <= 2) sweeps_straight(std::integral_constant<int, 1>{});
+      else if (nwmax <= 4) sweeps_straight(std::integral_constant<int, 2>{});
+      else sweeps_straight(std::integral_constant<int, 3>{});
+      swept = true;
+    }
+  }
+  if (__builtin_expect(!swept, 0))
   while (__ballot(act) != 0ull) {
     if (act) {
       impl = 0;
-#define WN_SWEEP_ONE(W, fw) do { \
-        const float u = wn_dot<NV>(W.J, a_lo, a_hi); \
-        const float fo = fw; \
-        float tt = ((u - W.aref) + W.R * fo) * W.nw; \
-        const float nf = -fo; \
-        float dl; \
-        PP_ROWS4(0, 1, 2, 3, W.A0); PP_ROWS4(4, 5, 6, 7, W.A1); PP_ROWS4(8, 9, 10, 11, W.A2); PP_ROWS4(12, 13, 14, 15, W.A3); \
-        asm volatile("v_max_f32 %0, %1, %2" : "=v"(dl) : "v"(tt), "v"(nf)); \
-        impl += imp_fixed((W.half * dl) * (2.0f * tt - dl), iq.qs); \
-        fw = fo + dl; \
-        wn_jt<NV>(W.J, dl, a_lo, a_hi); } while (0)
       // register-resident windows: pairs (see the cross tiles above), a last odd one alone
 #pragma unroll
       for (int j = 0; j < NW / 2; j++) if (2 * j < nwmax) {

@@ -1,5 +1,5 @@
 """The window chain's two launches in a rocprofv3 kernel trace (rocpd .db, first found under the directory) of a plain S24 bench line: mean / median /
-max of the last N launches of the assemble-only instance and of the window kernel (N = steps x cohorts: the timed window), and the cohort-step —
+max of the last N launches of the assemble-only instance and of the window kernel (N = steps x cohorts: the timed window), of the launch-order sorts among them, and the cohort-step —
 the span of those launches over the steps.     python tools/assemble_trace.py <dir> [steps] [cohorts]"""
 import glob
 import os
@@ -16,7 +16,8 @@ asm = [r for r in rows if "mjh_step_kernel" in r[0]][-n:]
 win = [r for r in rows if "mjh_window_kernel" in r[0]][-n:]
 print("| kernel | launches | mean (us) | median (us) | max (us) |")
 print("|---|---|---|---|---|")
-for lst in (asm, win):
+srt = [r for r in rows if "mjh_order_kernel" in r[0] and r[1] >= asm[0][1]]        # the launch-order sorts inside the timed window (every 32nd step and cohort)
+for lst in (asm, win) + ((srt,) if srt else ()):
     us = [(e - s) / 1e3 for _, s, e in lst]
     print(f"| `{lst[0][0].split('(')[0].replace('void ', '')}` | {len(us)} | {statistics.mean(us):.1f} | {statistics.median(us):.1f} | {max(us):.1f} |")
 t0 = min(r[1] for r in asm + win); t1 = max(r[2] for r in asm + win)
