@@ -178,6 +178,13 @@ typedef struct mjh_model {
   double *cam_pos, *cam_quat;   /* [3 ncam], [4 ncam]: camera frame in its body */
   double* cam_fovy;             /* [ncam] vertical field of view, degrees */
   char** cam_names;
+  /* ---- appended for rays against a mesh's own triangles (older fields keep their offsets) ----
+   * the triangles of the mesh file (or of mjh_builder_add_mesh's face list) as coordinates, moved into the frame of mesh_vert with
+   * the vertices and taken BEFORE those are de-duplicated and thinned; a triangle without area (two equal corners, or |e1 x e2| not
+   * above 1e-14 extent^2) is dropped.  A mesh given as points only has mesh_trinum 0; models assembled from tables have none. */
+  int nmeshtri;
+  int *mesh_triadr, *mesh_trinum;   /* [nmesh] */
+  double* mesh_tri;                 /* [9*nmeshtri]: a, b, c per triangle, in the frame of mesh_vert */
 } mjh_model;
 
 /* ------------------------------------------------- model builder (host) */
@@ -459,9 +466,9 @@ int mjh_set_body_pose(mjh_engine*, int env, int body, const double pos[3], const
  *   mesh geoms: invisible by default (mode 0); with mjh_ray_set_mesh_mode(engine, 1) a mesh geom is hit at the nearest non-negative x
  *     on its convex hull (mesh_plane: the hull of the kept vertices, the solid the narrow phase collides), and an origin inside hits
  *     the far surface, like the other bounded types.  mj_ray itself intersects the mesh file's triangles: for a convex mesh the two
- *     agree, for a non-convex one the ray sees the collision hull.  bodyexclude, flg_static, inactive slots and cutoff apply to
- *     mesh geoms like any other.  A mesh geom's hull is that of the model's mesh_vert: per-env geom sizes do not rescale it, as they
- *     do not in the narrow phase.
+ *     agree, for a non-convex one the ray sees the collision hull unless mjh_ray_set_mesh_surface (below) selects the triangles.
+ *     bodyexclude, flg_static, inactive slots and cutoff apply to mesh geoms like any other.  A mesh geom's hull is that of the
+ *     model's mesh_vert: per-env geom sizes do not rescale it, as they do not in the narrow phase.
  *   hfield geoms without an asset are invisible; mjh_ray_skipped_geoms counts what mode 0 cannot see.
  * A geom of a body whose spawn / destroy slot is inactive in an env is invisible there; geom sizes are the env's own where per-env
  * sizes are set (mjh_set_env_param).  Call-sequence rules are those of mjh_get_geom_state (a pending mjh_step1 is issued first and a
@@ -487,6 +494,21 @@ int mjh_ray_skipped_geoms(const mjh_model*);     /* geoms no ray can see in mesh
  * changes nothing.  Takes effect with the next ray call (the geom table of the mode is uploaded on that call's stream order). */
 int mjh_ray_set_mesh_mode(mjh_engine*, int mode);
 int mjh_ray_get_mesh_mode(const mjh_engine*);
+/* What a VISIBLE mesh geom is to a ray (the mesh mode keeps its meaning and its two values: 0 mesh geoms are invisible, 1 visible).
+ * MJH_RAY_SURFACE_HULL (default): the convex hull, as above.  MJH_RAY_SURFACE_TRIANGLES: a mesh geom whose asset has triangles
+ * (mesh_trinum > 0) is hit on them, as mj_ray does: dist is the smallest x >= 0 with pnt + x vec on ANY triangle of the mesh, from
+ * either side — so an origin inside a closed mesh hits the far surface, like the other bounded types, a hole the hull fills is open,
+ * and a mesh without volume (a flat panel: triangles but no hull planes) becomes visible.  A mesh geom without triangles keeps its
+ * hull, or stays invisible if it has no hull planes either.  In units of |vec|; bodyexclude, flg_static, cutoff, the slot masks and the
+ * lower geom id on a tie are unchanged; per-env geom sizes do not rescale a mesh, as in hull mode.  A triangle includes its edges
+ * with a few fp32 ulps of slack: a ray through a shared edge or vertex of a watertight mesh does not pass
+ * between two triangles.  mjh_ray and mjh_depth both obey the switch; mjh_ray_skipped_geoms keeps its mode-0 meaning.  The triangle
+ * tables (a bounding-volume hierarchy per mesh asset, built on the host) are uploaded by the first ray or depth call issued with the
+ * triangles selected: an engine that never selects them pays nothing.  Any other value returns MJH_ERR_ARG and changes nothing.
+ * [UPSTREAM, unverified here] MuJoCo 2.3.7's mj_rayMesh tests every face of the mesh, two-sided. */
+enum { MJH_RAY_SURFACE_HULL = 0, MJH_RAY_SURFACE_TRIANGLES = 1 };
+int mjh_ray_set_mesh_surface(mjh_engine*, int surface);
+int mjh_ray_get_mesh_surface(const mjh_engine*);
 
 /* Depth images: every env's view through a camera of the model, as tiled depth / segmentation images (the observation vision
  * policies train on).  The rays are generated on the device from the camera's intrinsics and its body's pose in each env: no ray
@@ -496,7 +518,7 @@ int mjh_ray_get_mesh_mode(const mjh_engine*);
  *   d.z = -1, so the ray parameter of the hit (in units of |d|) is the depth along the optical axis, what a depth buffer holds
  *   (range = 0); range = 1 multiplies it by |d|: the Euclidean distance from the camera origin.  A miss is depth -1, geomid -1.
  *   Everything else is mjh_ray's on the same engine: the semantics per geom type (a camera inside a geom sees its far surface),
- *   inactive slots, per-env geom sizes, mjh_ray_set_mesh_mode (it governs depth images too), the lower geom id on an exact fp32
+ *   inactive slots, per-env geom sizes, mjh_ray_set_mesh_mode and mjh_ray_set_mesh_surface (they govern depth images too), the lower geom id on an exact fp32
  *   tie, and the call-sequence rules (a pending mjh_step1 goes out first, a window hand-over is dropped).  Nothing of state,
  *   statistics, warm start or time is written.
  *   cull: each 8 x 8 pixel tile walks only the bounded geoms whose bounding sphere touches the tile's cone; cull = 0 makes every

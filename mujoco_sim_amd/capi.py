@@ -82,6 +82,9 @@ _ARRAYS5 = [("mesh_planeadr", "i", "nmesh"), ("mesh_planenum", "i", "nmesh"), ("
 # appended for depth cameras (behind mesh_plane)
 _INT_SIZES6 = ["ncam"]
 _ARRAYS6 = [("cam_bodyid", "i", "ncam"), ("cam_pos", "d", "3*ncam"), ("cam_quat", "d", "4*ncam"), ("cam_fovy", "d", "ncam")]
+# appended for rays against a mesh's own triangles (behind cam_names)
+_INT_SIZES7 = ["nmeshtri"]
+_ARRAYS7 = [("mesh_triadr", "i", "nmesh"), ("mesh_trinum", "i", "nmesh"), ("mesh_tri", "d", "9*nmeshtri")]
 
 
 class Model(C.Structure):
@@ -103,15 +106,17 @@ class Model(C.Structure):
         + [(n, C.c_int) for n in _INT_SIZES6]
         + [(n, c_int_p if t == "i" else c_double_p) for n, t, _ in _ARRAYS6]
         + [("cam_names", C.POINTER(C.c_char_p))]
+        + [(n, C.c_int) for n in _INT_SIZES7]
+        + [(n, c_int_p if t == "i" else c_double_p) for n, t, _ in _ARRAYS7]
     )
 
     def array(self, name):
         """numpy copy of a model array."""
         import numpy as np
 
-        for n, t, expr in _ARRAYS + _ARRAYS2 + _ARRAYS3 + _ARRAYS4 + _ARRAYS5 + _ARRAYS6:
+        for n, t, expr in _ARRAYS + _ARRAYS2 + _ARRAYS3 + _ARRAYS4 + _ARRAYS5 + _ARRAYS6 + _ARRAYS7:
             if n == name:
-                ln = eval(expr, {}, {k: getattr(self, k) for k in _INT_SIZES + _INT_SIZES2 + _INT_SIZES4 + _INT_SIZES5 + _INT_SIZES6})
+                ln = eval(expr, {}, {k: getattr(self, k) for k in _INT_SIZES + _INT_SIZES2 + _INT_SIZES4 + _INT_SIZES5 + _INT_SIZES6 + _INT_SIZES7})
                 ptr = getattr(self, n)
                 if ln == 0 or not ptr:
                     return np.zeros(0, dtype=np.int32 if t == "i" else np.float64)
@@ -230,6 +235,8 @@ SYMBOLS = [
     ("mjh_ray_skipped_geoms", C.c_int, [Model_p]),
     ("mjh_ray_set_mesh_mode", C.c_int, [_vp, C.c_int]),
     ("mjh_ray_get_mesh_mode", C.c_int, [_vp]),
+    ("mjh_ray_set_mesh_surface", C.c_int, [_vp, C.c_int]),
+    ("mjh_ray_get_mesh_surface", C.c_int, [_vp]),
     ("mjh_depth_default_options", None, [C.POINTER(DepthOptions)]),
     ("mjh_depth", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(DepthOptions), _vp, _vp]),
     ("mjh_depth_device", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(DepthOptions), _vp, _vp]),

@@ -15,7 +15,14 @@
 // are the same bits.
 static __device__ __forceinline__ float uniform(float x) { return ray_float(ray_uniform(ray_bits(x))); }
 
-__global__ __launch_bounds__(RAY_TILE) void mjh_depth_kernel(const DepthArgs A) {
+// TRI: the instance for scenes with triangle tables (mesh surface 1; dev_ray.h: ray_walk); the other one is the kernel as it was.
+// amdgpu_num_sgpr(96) (no effect on the instance without, which takes 89): with the triangle walk of dev_ray.h (a node and a triangle record in scalar registers on top of the cone and the
+// scene's pointers) the kernel would take 106 scalar registers, one wave per SIMD fewer than the 8 its LDS allows.  Capped, six values
+// of the prologue (read again once per staging pass and in the epilogue, never in the walk) live in lanes of one VGPR instead: no scratch.
+// Derived for the walk as it is: after a change to ray_trimesh / ray_tri look at -Rpass-analysis=kernel-resource-usage and at where the
+// v_readlane instructions land again, and drop or move the cap accordingly.
+template <bool TRI>
+__global__ __launch_bounds__(RAY_TILE) __attribute__((amdgpu_num_sgpr(96))) void mjh_depth_kernel(const DepthArgs A) {
   __shared__ float s_rec[RAY_PASS * RAY_REC];
   const RayScene& W = A.W;
   const int lane = (int)threadIdx.x;
@@ -67,7 +74,7 @@ __global__ __launch_bounds__(RAY_TILE) void mjh_depth_kernel(const DepthArgs A) 
       for (int k = 0; k < 3; k++) c[k] = gp[k];
 #pragma unroll
       for (int k = 0; k < 3; k++) s[k] = gsize[3*g + k];
-      keep = ray_verdict(W, gi, s, slotmask, rb) >= 0;
+      keep = ray_verdict<TRI>(W, gi, s, slotmask, rb, &A.T) >= 0;
       if (keep && A.cull && gi.x >= MJH_GEOM_SPHERE) {      // planes and height fields are never culled
         const float rel[3] = {c[0] - p[0], c[1] - p[1], c[2] - p[2]};
         keep = depth_cone_keep(axis, cosA, sinA, rel, rb);
@@ -79,7 +86,7 @@ __global__ __launch_bounds__(RAY_TILE) void mjh_depth_kernel(const DepthArgs A) 
       ray_store(s_rec + slot * RAY_REC, c, W.gmat + ((size_t)row * W.ngeom + g) * 9, s, rb, gi.x, gi.w, g);
     }
     __syncthreads();
-    ray_walk<false>(W, s_rec, __popcll(kept), p, v, vv, valid, best, bestg);
+    ray_walk<false, TRI>(W, s_rec, __popcll(kept), p, v, vv, valid, best, bestg, &A.T);
   }
   // dc.z = -1: the ray parameter is the depth along the optical axis; range: the distance from the camera origin
   if (A.range) best *= sqrtf(vv);
@@ -96,6 +103,7 @@ hipError_t mjh_launch_depth(hipStream_t st, const DepthArgs& A) {
   if (A.W.n <= 0 || A.width <= 0 || A.height <= 0) return hipErrorInvalidValue;
   const long long tx = (A.width + DEPTH_TILE - 1) / DEPTH_TILE, ty = (A.height + DEPTH_TILE - 1) / DEPTH_TILE, blocks = tx * ty * (long long)A.W.n;
   if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(mjh_depth_kernel, dim3((unsigned)blocks), dim3(RAY_TILE), 0, st, A);
+  if (A.T.mesh) hipLaunchKernelGGL(mjh_depth_kernel<true>, dim3((unsigned)blocks), dim3(RAY_TILE), 0, st, A);
+  else hipLaunchKernelGGL(mjh_depth_kernel<false>, dim3((unsigned)blocks), dim3(RAY_TILE), 0, st, A);
   return hipGetLastError();
 }

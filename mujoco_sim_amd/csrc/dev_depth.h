@@ -15,6 +15,7 @@ struct DepthArgs {
   int range, cull;                 // range: report the distance from the camera origin, not the depth; cull: the tile-cone test
   int cam_body; float cam_pos[3], cam_quat[4];   // camera frame in its body
   float scale;                     // tan(fovy / 2) / height: half the side of a (square) pixel on the plane z = -1
+  RayTris T;
 };
 
 hipError_t mjh_launch_depth(hipStream_t st, const DepthArgs& A);   // depth.hip

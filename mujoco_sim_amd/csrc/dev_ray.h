@@ -10,10 +10,12 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/mjhip.h"
+#include "ray_bvh.h"
 
 #define RAY_TILE 64   // rays per workgroup: one wavefront, one ray per lane
 #define RAY_PASS 64   // geom records one staging pass holds (one geom per lane)
 #define RAY_REC 20    // floats of a record (ray_store)
+#define RAY_TYPE_TRIMESH 8   // internal type of a mesh geom seen as its own triangles (not a public mjh_geom value): w = mesh id, RayScene::trimesh
 
 struct RayHField { int nrow, ncol, adr, pad; float size[4]; };   // size: radius_x, radius_y, elevation_z, base_z
 
@@ -34,12 +36,17 @@ struct RayScene {
   float cutoff;                    // > 0: a reported value beyond it is a miss
 };
 
+// mesh surface 1 (ray_bvh.h): [nmesh], the meshes' nodes, four float4 per triangle; all null unless the scene's geom table holds
+// RAY_TYPE_TRIMESH rows.  Beside RayScene, not in it: that struct's layout is mirrored by the host tests.
+struct RayTris { const RayTriMesh* mesh; const RayNode* nodes; const float4* tris; };
+
 struct RayArgs {
   RayScene W;
   const float *pnt, *vec;          // [nray][3], or [n][nray][3] with per_env
   float* dist; int* geomid;        // [n][nray]
   int nray, per_env;
   int site_body; float site_pos[3], site_quat[4];   // site frame in its body (site_body < 0: rays are given in the world frame)
+  RayTris T;
 };
 
 hipError_t mjh_launch_ray(hipStream_t st, const RayArgs& A);   // ray.hip
@@ -261,8 +268,6 @@ RDEV float ray_hfield(const float* p, const float* v, const RayHField& H, const 
   return best;
 }
 
-// ---- a ray through the geoms of an env
-
 // a wave-uniform value read into a scalar register (the identity in a host compile)
 RDEV int ray_uniform(int x) {
 #ifdef __HIP_DEVICE_COMPILE__
@@ -273,6 +278,84 @@ RDEV int ray_uniform(int x) {
 }
 RDEV int ray_bits(float x) { return __builtin_bit_cast(int, x); }
 RDEV float ray_float(int x) { return __builtin_bit_cast(float, x); }
+
+// A mesh's own triangles (ray_bvh.h: the records, the threaded BVH and the slack).  ray_tri is Moeller-Trumbore in fp32, two-sided:
+// with P = v x e2, det = e1.P, T = p - a, Q = T x e1 the hit is u = T.P / det, w = v.Q / det, x = e2.Q / det.
+//   parallel: |det| <= 2^-22 |e1|_1 |e2|_1 |v|_1 is rounding noise of the three products of det (two ulps of their scale): a miss.
+//   edges: u >= -eu, w >= -ew, u + w <= 1 + eu + ew with eu = 2^-20 L |v|_1 |e2|_1 / |det|, ew likewise with |e1|_1, L = |p|_1 + R1 (R1:
+//     the mesh's largest corner 1-norm).  Eight ulps of the operand scale of the numerator: T carries half an ulp of L from the
+//     subtraction and another from the stored corner (1.2e-7 L |P|_1), a component of P three roundings of |v||e2| (0.9e-7 |v|_1 |e2|_1
+//     each), the dot product three more of its terms (2e-7), det the same relative to |e1|_1 <= L (3e-7, times u <= 1): 7.4e-7 in
+//     all in the worst case, under 2^-20 = 9.5e-7.  Two triangles that share an edge store it from different corners (a + e1 here,
+//     a' + e2' there): that is the stored-corner term.  So on a shared edge or vertex at least one of the neighbours takes the point.
+//   box: the hit point p + x v, as fp32 computes it, must lie in the triangle's own box widened by sp = 2^-21 |p|_1 (the record's
+//     box carries 2^-21 R1 already).  This bounds what the edge slack can accept for a grazing ray (eu grows as 1 / det), and it is
+//     what makes pruning exact (ray_bvh.h): an accepted x lies inside every enclosing node's widened box.
+// sp, L and vn = |v|_1 are the ray's, computed once per geom.
+RDEV float ray_tri(const float* p, const float* v, float vn, float L, float sp, const float4 q0, const float4 q1, const float4 q2, const float4 q3) {
+  const float e1[3] = {q1.x, q1.y, q1.z}, e2[3] = {q2.x, q2.y, q2.z};
+  const float n1 = q0.w, n2 = fabsf(e2[0]) + fabsf(e2[1]) + fabsf(e2[2]);
+  const float P[3] = {v[1]*e2[2] - v[2]*e2[1], v[2]*e2[0] - v[0]*e2[2], v[0]*e2[1] - v[1]*e2[0]};
+  const float det = e1[0]*P[0] + e1[1]*P[1] + e1[2]*P[2];
+  if (!(fabsf(det) > 2.38418579e-7f * n1 * n2 * vn)) return -1.0f;
+  const float inv = 1.0f / det;
+  const float T[3] = {p[0] - q0.x, p[1] - q0.y, p[2] - q0.z};
+  const float Q[3] = {T[1]*e1[2] - T[2]*e1[1], T[2]*e1[0] - T[0]*e1[2], T[0]*e1[1] - T[1]*e1[0]};
+  const float u = (T[0]*P[0] + T[1]*P[1] + T[2]*P[2]) * inv, w = (v[0]*Q[0] + v[1]*Q[1] + v[2]*Q[2]) * inv;
+  const float x = (e2[0]*Q[0] + e2[1]*Q[1] + e2[2]*Q[2]) * inv;
+  const float ek = 9.53674316e-7f * L * vn * fabsf(inv), eu = ek * n2, ew = ek * n1;
+  const float X[3] = {p[0] + x * v[0], p[1] + x * v[1], p[2] + x * v[2]};
+  const bool in = u >= -eu && w >= -ew && u + w <= 1.0f + eu + ew && x >= 0.0f;
+  const bool box = X[0] >= q1.w - sp && X[1] >= q2.w - sp && X[2] >= q3.x - sp && X[0] <= q3.y + sp && X[1] <= q3.z + sp && X[2] <= q3.w + sp;
+  return in && box ? x : -1.0f;
+}
+
+// The smallest x in [0, bound] with p + x v on a triangle of the mesh, or -1; bound: the ray's best hit so far (3e38: none) — x is the
+// same parameter in every geom frame, so a node the ray enters beyond it holds nothing the walk would take (it replaces a record only
+// for x < best).  One forward scan of the mesh's nodes (ray_bvh.h): i -> i + 1 or i -> skip > i, so it ends after at most nnode steps
+// whatever the tables hold; no stack, no private array.  In the kernels the mesh is wave-uniform: i lives in a scalar register, a node
+// and a triangle come by scalar loads, the subtree is skipped when NO lane of the wave wants it (a lane that did not want a leaf
+// tests its triangles all the same: by the argument of ray_bvh.h it finds nothing below its bound there).  A node's slab test uses
+// the reciprocal direction (+-inf for a zero component: the products are then +-inf, or NaN for an origin on the slab's face, which
+// fminf / fmaxf drop: inside) and the box widened by sn = 3 sp.
+RDEV float ray_trimesh(const float* p, const float* v, const RayTriMesh& M, const RayNode* __restrict__ nodes, const float4* __restrict__ tris, float bound) {
+  const float vn = fabsf(v[0]) + fabsf(v[1]) + fabsf(v[2]), pn = fabsf(p[0]) + fabsf(p[1]) + fabsf(p[2]);
+  const float L = pn + M.r1, sp = RAY_SLACK * pn, sn = RAY_NODE_SLACK * sp;
+  const float iv[3] = {1.0f / v[0], 1.0f / v[1], 1.0f / v[2]};
+  const float pl[3] = {p[0] + sn, p[1] + sn, p[2] + sn}, ph[3] = {p[0] - sn, p[1] - sn, p[2] - sn};
+  float cur = -1.0f, lim = bound;
+  const int n = M.nnode;
+  int i = 0;
+  while (i < n) {
+    const RayNode N = nodes[i];
+    float lo = -3.0e38f, hi = 3.0e38f;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      const float a = (N.bmin[k] - pl[k]) * iv[k], b = (N.bmax[k] - ph[k]) * iv[k];
+      lo = fmaxf(lo, fminf(a, b)); hi = fminf(hi, fmaxf(a, b));
+    }
+    const bool hit = lo <= hi && hi >= 0.0f && lo <= lim;
+#ifdef __HIP_DEVICE_COMPILE__
+    const bool go = __builtin_amdgcn_ballot_w64(hit) != 0;      // (wave-uniform)
+#else
+    const bool go = hit;
+#endif
+    if (!go) { i = ray_uniform(N.skip); continue; }
+    const int leaf = ray_uniform(N.leaf);
+    if (leaf >= 0) {
+      const float4* q = tris + (size_t)4 * (size_t)(leaf >> 3);
+      const int cnt = leaf & 7;
+      for (int t = 0; t < cnt; t++) {
+        const float x = ray_tri(p, v, vn, L, sp, q[4*t], q[4*t + 1], q[4*t + 2], q[4*t + 3]);
+        if (x >= 0.0f && x <= lim) { cur = x; lim = x; }
+      }
+    }
+    i = i + 1;
+  }
+  return cur;
+}
+
+// ---- a ray through the geoms of an env
 
 // world origin o[3] and rotation S[9] (row-major, world = S local) of a frame (pos, quat) given in a body (a site, a camera), from the
 // body's exported world pose bp, bq.  A macro, not a function: the kernels' bits depend on it.  As an RDEV function (pos / quat as
@@ -294,8 +377,10 @@ RDEV float ray_float(int x) { return __builtin_bit_cast(float, x); }
 
 // the verdict on a geom (its ginfo row gi, its size s in the env, the env's slot mask): the type a ray sees, or -1 for a geom
 // invisible in this env; rb: the radius of its bounding sphere (of a mesh: of the model's mesh_vert — per-env sizes do not rescale a
-// mesh, in the narrow phase neither), a little larger than the geom's: the reject of the walk must never cost a hit
-RDEV int ray_verdict(const RayScene& W, const int4 gi, const float* s, unsigned slotmask, float& rb) {
+// mesh, in the narrow phase neither), a little larger than the geom's: the reject of the walk must never cost a hit.  TRI: the geom table
+// may hold RAY_TYPE_TRIMESH rows (mesh surface 1); without it the function is the code it was before that type existed
+template <bool TRI = false>
+RDEV int ray_verdict(const RayScene& W, const int4 gi, const float* s, unsigned slotmask, float& rb, const RayTris* T = nullptr) {
   rb = 0.0f;
   if (gi.x == MJH_GEOM_SPHERE) rb = s[0];
   else if (gi.x == MJH_GEOM_CAPSULE) rb = s[0] + s[1];
@@ -303,6 +388,7 @@ RDEV int ray_verdict(const RayScene& W, const int4 gi, const float* s, unsigned 
   else if (gi.x == MJH_GEOM_CYLINDER) rb = sqrtf(s[0]*s[0] + s[1]*s[1]);
   else if (gi.x == MJH_GEOM_BOX) rb = sqrtf(s[0]*s[0] + s[1]*s[1] + s[2]*s[2]);
   else if (gi.x == MJH_GEOM_MESH) rb = W.mesh[gi.w].rbound;
+  if constexpr (TRI) { if (gi.x == RAY_TYPE_TRIMESH) rb = T->mesh[gi.w].rbound; }      // (of the triangles' corners: the kept vertices of `mesh` are an inner approximation)
   rb *= 1.001f;
   const bool slot_off = gi.y >= W.sbase && gi.y - W.sbase < 32 && ((slotmask >> (gi.y - W.sbase)) & 1u);
   const bool visible = gi.x >= 0 && gi.y != W.bodyexclude && (W.flg_static || !gi.z) && !slot_off;
@@ -328,8 +414,11 @@ RDEV void ray_store(float* rec, const float* pos, const float* mat, const float*
 // the walk: the world-frame ray (p, v; vv = |v|^2; valid: 0 < vv < inf) against `cnt` staged records, in their order; best / bestg
 // keep the nearest hit, the earlier record on a tie.  In the kernels every lane of a wave walks the same records: the record index is
 // wave-uniform, so the type switch is a scalar branch and the record reads are LDS broadcasts.  SKIP: records of type -1 occur.
-template <bool SKIP>
-RDEV void ray_walk(const RayScene& W, const float* recs, int cnt, const float* p, const float* v, float vv, bool valid, float& best, int& bestg) {
+// TRI: records of RAY_TYPE_TRIMESH occur (mesh surface 1).  The kernels are compiled once with and once without it, and a launch takes
+// the instance without unless the scene has triangle tables: as one more case of the one switch the walk cost the scenes that have no
+// such record 1.5 - 4.6 %, through the compiler's register and branch layout alone.
+template <bool SKIP, bool TRI = false>
+RDEV void ray_walk(const RayScene& W, const float* recs, int cnt, const float* p, const float* v, float vv, bool valid, float& best, int& bestg, const RayTris* T = nullptr) {
   for (int j = 0; j < cnt; j++) {
     const float* rec = recs + j * RAY_REC;
     const int type = ray_uniform(ray_bits(rec[16]));
@@ -358,7 +447,14 @@ RDEV void ray_walk(const RayScene& W, const float* recs, int cnt, const float* p
             const RayMesh Mh = W.mesh[ray_uniform(ray_bits(rec[17]))];
             x = ray_convex(lp, lv, W.planes + Mh.adr, Mh.num);
           } break;
-          default: break;
+          default:
+            if constexpr (TRI) {
+              if (type == RAY_TYPE_TRIMESH) {      // the mesh id is wave-uniform: its table row, the nodes and the triangles come by scalar loads
+                const RayTriMesh Mt = T->mesh[ray_uniform(ray_bits(rec[17]))];
+                x = ray_trimesh(lp, lv, Mt, T->nodes + Mt.node, T->tris + (size_t)4 * (size_t)Mt.tri, bestg < 0 ? 3.0e38f : best);
+              }
+            }
+            break;
         }
       }
     } else if (valid) {

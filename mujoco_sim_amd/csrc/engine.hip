@@ -117,6 +117,11 @@ struct mjh_engine {
   // mesh mode (mjh_ray_set_mesh_mode): the geom table of mode 1 (mesh geoms typed MJH_GEOM_MESH with their mesh id; the mode-0 table itself
   // in a model without hull planes), the per-mesh table and the fp32 planes — uploaded with the others; a mode change switches tables
   int ray_mesh_mode = 0; int4* ray_ginfo_mesh = nullptr; RayMesh* ray_mesh = nullptr; float4* ray_planes = nullptr;
+  // mesh surface (mjh_ray_set_mesh_surface): the third geom table (mesh geoms whose asset has triangles typed RAY_TYPE_TRIMESH; the mode-1
+  // table itself in a model without triangles), the per-mesh table, the BVH nodes and the triangle records (ray_bvh.h) — built and
+  // uploaded by the first launch issued with the triangles selected, freed with the engine
+  int ray_mesh_surface = 0; bool ray_tri_ready = false; std::vector<int4> ray_gi_mesh_host;
+  int4* ray_ginfo_tri = nullptr; RayTriMesh* ray_trimesh = nullptr; RayNode* ray_nodes = nullptr; float4* ray_tris = nullptr;
   float* ray_io = nullptr; size_t ray_io_floats = 0;
 };
 
@@ -1913,9 +1918,61 @@ static int ray_tables(mjh_engine* e) {
       HIPCHK(hipMemcpy(e->ray_planes, pl.data(), pl.size() * sizeof(float4), hipMemcpyHostToDevice));
     }
   }
+  e->ray_gi_mesh_host = gi;
   e->ray_ready = true;
   return MJH_OK;
 }
+// the tables of mesh surface 1 (after ray_tables): a BVH per mesh asset with triangles (ray_bvh.h), all of them in one node and one
+// triangle array, and the geom table that types those assets' geoms RAY_TYPE_TRIMESH — a mesh geom without triangles keeps its row of the
+// mode-1 table (its hull, or invisible)
+static int ray_tri_tables(mjh_engine* e) {
+  if (e->ray_tri_ready) return MJH_OK;
+  const mjh_model* m = e->model;
+  e->ray_ginfo_tri = e->ray_ginfo_mesh;
+  if (m->nmesh > 0 && m->nmeshtri > 0 && m->mesh_tri && m->mesh_triadr && m->mesh_trinum && m->geom_dataid) {
+    std::vector<RayTriMesh> mt((size_t)m->nmesh, RayTriMesh{0, 0, 0, 0, 0.0f, 0.0f, 0.0f, 0.0f});
+    std::vector<RayNode> nodes; std::vector<float> tris;
+    for (int i = 0; i < m->nmesh; i++) {
+      const int adr = m->mesh_triadr[i], num = m->mesh_trinum[i];
+      if (!(adr >= 0 && num > 0 && (long long)adr + num <= m->nmeshtri)) continue;
+      RayBvh B;
+      if (!ray_bvh_build(m->mesh_tri + 9 * (size_t)adr, num, B)) { mjh_set_error("mjh_ray: the triangles of mesh " + std::to_string(i) + " give no valid BVH (non-finite coordinates?)"); return MJH_ERR_ARG; }
+      if (nodes.size() + B.nodes.size() > 0x7fffffffull || tris.size() / RAY_TRI_FLOATS + (size_t)num > 0x0fffffffull) { mjh_set_error("mjh_ray: too many mesh triangles"); return MJH_ERR_ARG; }
+      mt[i] = RayTriMesh{(int)nodes.size(), (int)B.nodes.size(), (int)(tris.size() / RAY_TRI_FLOATS), num, B.rbound, B.r1, 0.0f, 0.0f};
+      nodes.insert(nodes.end(), B.nodes.begin(), B.nodes.end());
+      tris.insert(tris.end(), B.tris.begin(), B.tris.end());
+    }
+    std::vector<int4> gi = e->ray_gi_mesh_host;
+    bool any = false;
+    for (int g = 0; g < m->ngeom; g++) {
+      const int id = m->geom_dataid[g];
+      if (m->geom_type[g] == MJH_GEOM_MESH && id >= 0 && id < m->nmesh && mt[id].nnode > 0) { gi[g].x = RAY_TYPE_TRIMESH; gi[g].w = id; any = true; }
+    }
+    if (any) {
+      // (the engine's pointers are set once all four tables are filled: a failed allocation or copy leaves the hull's table in place)
+      int4* d_gi = nullptr; RayTriMesh* d_mt = nullptr; RayNode* d_nodes = nullptr; float4* d_tris = nullptr;
+      int rc = dev_alloc(e, &d_gi, gi.size(), false);
+      if (!rc) rc = dev_alloc(e, &d_mt, mt.size(), false);
+      if (!rc) rc = dev_alloc(e, &d_nodes, nodes.size(), false);
+      if (!rc) rc = dev_alloc(e, &d_tris, tris.size() / 4, false);
+      if (rc) return rc;
+      HIPCHK(hipMemcpy(d_gi, gi.data(), gi.size() * sizeof(int4), hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(d_mt, mt.data(), mt.size() * sizeof(RayTriMesh), hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(d_nodes, nodes.data(), nodes.size() * sizeof(RayNode), hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(d_tris, tris.data(), tris.size() * sizeof(float), hipMemcpyHostToDevice));
+      e->ray_ginfo_tri = d_gi; e->ray_trimesh = d_mt; e->ray_nodes = d_nodes; e->ray_tris = d_tris;
+    }
+  }
+  e->ray_tri_ready = true;
+  return MJH_OK;
+}
+extern "C" int mjh_ray_set_mesh_surface(mjh_engine* e, int surface) {
+  ENG(e);
+  if (surface != MJH_RAY_SURFACE_HULL && surface != MJH_RAY_SURFACE_TRIANGLES) { mjh_set_error("mjh_ray_set_mesh_surface: surface must be 0 (hull) or 1 (triangles)"); return MJH_ERR_ARG; }
+  e->ray_mesh_surface = surface;      // (the next ray launch takes the surface's geom table by value; the triangle tables are built by that launch)
+  return MJH_OK;
+}
+extern "C" int mjh_ray_get_mesh_surface(const mjh_engine* e) { return e ? e->ray_mesh_surface : 0; }
 extern "C" int mjh_ray_set_mesh_mode(mjh_engine* e, int mode) {
   ENG(e);
   if (mode != 0 && mode != 1) { mjh_set_error("mjh_ray_set_mesh_mode: mode must be 0 or 1"); return MJH_ERR_ARG; }
@@ -1936,9 +1993,10 @@ static int ray_check(const mjh_engine* e, int env0, int n, int nray, const void*
 }
 // The launch chain of mjh_ray_device and mjh_depth_device: the position-stage launch of the env range (PH_FKONLY with XF_GEOM, plus
 // XF_BODY when `bodies`: a site's or a camera's frame) into the engine's export scratch, exactly as fk_export issues it; the caller's
-// kernel follows on the same stream and reads what *W names.  Nothing of the envs' state, statistics or time is written.
-static int ray_scene(mjh_engine* e, int env0, int n, bool bodies, int bodyexclude, int flg_static, double cutoff, RayScene* W) {
+// kernel follows on the same stream and reads what *W (and, with mesh surface 1, *T) names.  Nothing of the envs' state, statistics or time is written.
+static int ray_scene(mjh_engine* e, int env0, int n, bool bodies, int bodyexclude, int flg_static, double cutoff, RayScene* W, RayTris* T) {
   int rc = ray_tables(e);
+  if (!rc && e->ray_mesh_surface == MJH_RAY_SURFACE_TRIANGLES) rc = ray_tri_tables(e);
   if (rc) return rc;
   const int ng = e->M.ngeom, nb = e->M.nbody;
   const size_t fg = (size_t)n * 3 * ng, fm = (size_t)n * 9 * ng, fx = bodies ? (size_t)n * 3 * nb : 0, fq = bodies ? (size_t)n * 4 * nb : 0;
@@ -1955,8 +2013,10 @@ static int ray_scene(mjh_engine* e, int env0, int n, bool bodies, int bodyexclud
   if (rc) return rc;
   if (e->S.p_geom_size) { W->size = e->S.p_geom_size; W->size_stride = e->S.p_stride; } else { W->size = e->dF + e->M.o_geom_size; W->size_stride = 0; }
   W->slot_mask = e->S.slot_mask; W->sbase = nb > 32 ? nb - 32 : 0;
-  W->ginfo = e->ray_mesh_mode ? e->ray_ginfo_mesh : e->ray_ginfo; W->hf = e->ray_hf; W->hf_data = e->ray_hfdata;
+  const bool tri = e->ray_mesh_mode && e->ray_mesh_surface == MJH_RAY_SURFACE_TRIANGLES;
+  W->ginfo = !e->ray_mesh_mode ? e->ray_ginfo : (tri ? e->ray_ginfo_tri : e->ray_ginfo_mesh); W->hf = e->ray_hf; W->hf_data = e->ray_hfdata;
   W->mesh = e->ray_mesh; W->planes = e->ray_planes;
+  T->mesh = tri ? e->ray_trimesh : nullptr; T->nodes = tri ? e->ray_nodes : nullptr; T->tris = tri ? e->ray_tris : nullptr;
   W->env0 = env0; W->n = n; W->ngeom = ng; W->nbody = nb;
   W->bodyexclude = bodyexclude; W->flg_static = flg_static ? 1 : 0; W->cutoff = cutoff > 0 ? (float)cutoff : 0.0f;
   return MJH_OK;
@@ -1978,7 +2038,7 @@ extern "C" int mjh_ray_device(mjh_engine* e, int env0, int n, int nray, const fl
   if (opt) o = *opt;
   const mjh_model* m = e->model;
   RayArgs A{};
-  rc = ray_scene(e, env0, n, o.site >= 0, o.bodyexclude, o.flg_static, o.cutoff, &A.W);
+  rc = ray_scene(e, env0, n, o.site >= 0, o.bodyexclude, o.flg_static, o.cutoff, &A.W, &A.T);
   if (rc) return rc;
   A.pnt = d_pnt; A.vec = d_vec; A.dist = d_dist; A.geomid = d_geomid;
   A.nray = nray; A.per_env = o.per_env ? 1 : 0;
@@ -2041,7 +2101,7 @@ extern "C" int mjh_depth_device(mjh_engine* e, int env0, int n, const mjh_depth_
   if (rc) return rc;
   const mjh_model* m = e->model;
   DepthArgs A{};
-  rc = ray_scene(e, env0, n, true, o.bodyexclude, o.flg_static, o.cutoff, &A.W);
+  rc = ray_scene(e, env0, n, true, o.bodyexclude, o.flg_static, o.cutoff, &A.W, &A.T);
   if (rc) return rc;
   A.depth = d_depth; A.geomid = d_geomid;
   A.width = o.width; A.height = o.height; A.range = o.range ? 1 : 0; A.cull = o.cull ? 1 : 0;

@@ -42,6 +42,7 @@ struct BMesh {
   double volume, inertia[3];       // unit density
   double rbound;
   std::vector<double> plane;       // hull planes of `vert` (n, d per plane; hull_planes below), own frame
+  std::vector<double> tri;         // the mesh's own triangles (a, b, c per triangle: 9 doubles), own frame; empty for a point cloud
 };
 struct BEq { int type = MJH_EQ_JOINT; int j1 = -1, j2 = -1; double poly[5] = {0, 0, 0, 0, 0};        // joint coupling: joints j1, j2
               int b1 = 0, b2 = 0; double anchor[3] = {0, 0, 0}; double torquescale = 1; };       // connect / weld: bodies b1, b2
@@ -327,6 +328,18 @@ static int add_mesh_impl(mjh_builder* b, std::vector<double> v, const int* face,
     double d[3] = {v[3*i]-com[0], v[3*i+1]-com[1], v[3*i+2]-com[2]}, r[3];
     hm::rotvecT(r, R, d);
     v[3*i] = r[0]; v[3*i+1] = r[1]; v[3*i+2] = r[2];
+  }
+  // the mesh's own triangles, as coordinates (what a ray sees with MJH_RAY_SURFACE_TRIANGLES), taken here: the de-duplication below
+  // renumbers the vertices.  A triangle without area is dropped: two equal corners, or |e1 x e2| not above 1e-14 extent^2
+  {
+    const double ext2 = ext[0]*ext[0] + ext[1]*ext[1] + ext[2]*ext[2];
+    for (int f = 0; f < nface; f++) {
+      const double *A = &v[3*face[3*f]], *Bv = &v[3*face[3*f+1]], *Cv = &v[3*face[3*f+2]];
+      const double e1[3] = {Bv[0]-A[0], Bv[1]-A[1], Bv[2]-A[2]}, e2[3] = {Cv[0]-A[0], Cv[1]-A[1], Cv[2]-A[2]};
+      double n[3]; hm::cross(n, e1, e2);
+      if (!(std::sqrt(hm::dot3(n, n)) > 1e-14 * ext2)) continue;
+      M.tri.insert(M.tri.end(), A, A + 3); M.tri.insert(M.tri.end(), Bv, Bv + 3); M.tri.insert(M.tri.end(), Cv, Cv + 3);
+    }
   }
   // The mesh collides as its convex hull, and the hull's support mapping only ever returns hull vertices: keep the
   // vertices that are extreme along a dense direction set (Fibonacci sphere + the 26 axis/diagonal directions).  An
@@ -751,12 +764,15 @@ extern "C" mjh_model* mjh_builder_compile(mjh_builder* B) {
   std::vector<std::string> geom_names(ngeom);
   std::vector<int> geom_dataid(ngeom, -1), mesh_vertadr, mesh_vertnum;
   std::vector<double> mesh_vert, mesh_plane;
-  std::vector<int> mesh_planeadr, mesh_planenum;
+  std::vector<int> mesh_planeadr, mesh_planenum, mesh_triadr, mesh_trinum;
+  std::vector<double> mesh_tri;
   for (const BMesh& Mh : B->meshes) {
     mesh_vertadr.push_back((int)mesh_vert.size() / 3); mesh_vertnum.push_back((int)Mh.vert.size() / 3);
     mesh_vert.insert(mesh_vert.end(), Mh.vert.begin(), Mh.vert.end());
     mesh_planeadr.push_back((int)mesh_plane.size() / 4); mesh_planenum.push_back((int)Mh.plane.size() / 4);
     mesh_plane.insert(mesh_plane.end(), Mh.plane.begin(), Mh.plane.end());
+    mesh_triadr.push_back((int)mesh_tri.size() / 9); mesh_trinum.push_back((int)Mh.tri.size() / 9);
+    mesh_tri.insert(mesh_tri.end(), Mh.tri.begin(), Mh.tri.end());
   }
   for (int g = 0; g < ngeom; g++) {
     const BGeom& G = B->geoms[gorder[g]];
@@ -1113,6 +1129,8 @@ extern "C" mjh_model* mjh_builder_compile(mjh_builder* B) {
   SETI(geom_dataid); SETI(mesh_vertadr); SETI(mesh_vertnum); SETI(mesh_vert);
   m->nmeshplane = (int)mesh_plane.size() / 4;
   SETI(mesh_planeadr); SETI(mesh_planenum); SETI(mesh_plane);
+  m->nmeshtri = (int)mesh_tri.size() / 9;
+  SETI(mesh_triadr); SETI(mesh_trinum); SETI(mesh_tri);
 #undef SETI
   {   // height fields: elevation normalised to [0, 1] (minus the minimum, divided by the range when it is non-zero)
     const int nh = (int)B->hfields.size();
@@ -1283,6 +1301,9 @@ extern "C" mjh_model* mjh_model_replicate(const mjh_model* a, int G) {
   m->mesh_planeadr = ialloc(a->nmesh); m->mesh_planenum = ialloc(a->nmesh); m->mesh_plane = dalloc((size_t)4 * a->nmeshplane);
   for (int i = 0; i < a->nmesh; i++) { m->mesh_planeadr[i] = a->mesh_planeadr ? a->mesh_planeadr[i] : 0; m->mesh_planenum[i] = a->mesh_planenum ? a->mesh_planenum[i] : 0; }
   if (a->mesh_plane) cpd(m->mesh_plane, a->mesh_plane, (size_t)4 * a->nmeshplane);
+  m->nmeshtri = a->mesh_tri && a->mesh_triadr && a->mesh_trinum ? a->nmeshtri : 0;
+  m->mesh_triadr = ialloc(a->nmesh); m->mesh_trinum = ialloc(a->nmesh); m->mesh_tri = dalloc((size_t)9 * m->nmeshtri);
+  if (m->nmeshtri) { for (int i = 0; i < a->nmesh; i++) { m->mesh_triadr[i] = a->mesh_triadr[i]; m->mesh_trinum[i] = a->mesh_trinum[i]; } cpd(m->mesh_tri, a->mesh_tri, (size_t)9 * m->nmeshtri); }
   m->body_names = dupnames(bnames); m->jnt_names = dupnames(jnames); m->geom_names = dupnames(gnames);
   m->body_mocapid = ialloc(NB);
   for (int b = 0; b < NB; b++) m->body_mocapid[b] = -1;
@@ -1303,7 +1324,8 @@ extern "C" void mjh_model_destroy(mjh_model* m) {
     m->geom_dataid, m->mesh_vertadr, m->mesh_vertnum, m->mesh_vert,
     m->site_bodyid, m->site_pos, m->site_quat, m->sensor_type, m->sensor_objid, m->sensor_adr, m->body_mocapid,
     m->hfield_nrow, m->hfield_ncol, m->hfield_adr, m->hfield_size, m->hfield_data,
-    m->mesh_planeadr, m->mesh_planenum, m->mesh_plane, m->cam_bodyid, m->cam_pos, m->cam_quat, m->cam_fovy};
+    m->mesh_planeadr, m->mesh_planenum, m->mesh_plane, m->cam_bodyid, m->cam_pos, m->cam_quat, m->cam_fovy,
+    m->mesh_triadr, m->mesh_trinum, m->mesh_tri};
   for (void* p : ptrs) std::free(p);
   auto freen = [](char** n, int c) { if (!n) return; for (int i = 0; i < c; i++) std::free(n[i]); std::free(n); };
   freen(m->body_names, m->nbody); freen(m->jnt_names, m->njnt); freen(m->geom_names, m->ngeom);

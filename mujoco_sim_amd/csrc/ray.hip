@@ -10,7 +10,8 @@
 
 // One workgroup (one wavefront) per (env, tile of RAY_TILE rays), one ray per lane.  The env's geom records are staged into LDS,
 // RAY_PASS geoms per pass (one per lane); then every lane walks the records together (dev_ray.h: ray_walk).  Envs are addressed by env
-// id (env0 + row of the launch).
+// id (env0 + row of the launch).  TRI: the instance for scenes with triangle tables (mesh surface 1; dev_ray.h: ray_walk).
+template <bool TRI>
 __global__ __launch_bounds__(RAY_TILE) void mjh_ray_kernel(const RayArgs A) {
   __shared__ float s_rec[RAY_PASS * RAY_REC];
   const RayScene& W = A.W;
@@ -45,11 +46,11 @@ __global__ __launch_bounds__(RAY_TILE) void mjh_ray_kernel(const RayArgs A) {
       const int4 gi = W.ginfo[g];
       const float s[3] = {gsize[3*g], gsize[3*g + 1], gsize[3*g + 2]};
       float rb;
-      const int type = ray_verdict(W, gi, s, slotmask, rb);
+      const int type = ray_verdict<TRI>(W, gi, s, slotmask, rb, &A.T);
       ray_store(s_rec + lane * RAY_REC, W.gpos + ((size_t)row * W.ngeom + g) * 3, W.gmat + ((size_t)row * W.ngeom + g) * 9, s, rb, type, gi.w, g);
     }
     __syncthreads();
-    ray_walk<true>(W, s_rec, min(RAY_PASS, W.ngeom - base), p, v, vv, valid, best, bestg);
+    ray_walk<true, TRI>(W, s_rec, min(RAY_PASS, W.ngeom - base), p, v, vv, valid, best, bestg, &A.T);
   }
   if (W.cutoff > 0.0f && best > W.cutoff) bestg = -1;      // rangefinder cutoff: a hit beyond it is a miss
   if (bestg < 0) best = -1.0f;
@@ -62,6 +63,7 @@ __global__ __launch_bounds__(RAY_TILE) void mjh_ray_kernel(const RayArgs A) {
 hipError_t mjh_launch_ray(hipStream_t st, const RayArgs& A) {
   const long long ntile = ((long long)A.nray + RAY_TILE - 1) / RAY_TILE, blocks = ntile * (long long)A.W.n;
   if (A.W.n <= 0 || A.nray <= 0 || blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(mjh_ray_kernel, dim3((unsigned)blocks), dim3(RAY_TILE), 0, st, A);
+  if (A.T.mesh) hipLaunchKernelGGL(mjh_ray_kernel<true>, dim3((unsigned)blocks), dim3(RAY_TILE), 0, st, A);
+  else hipLaunchKernelGGL(mjh_ray_kernel<false>, dim3((unsigned)blocks), dim3(RAY_TILE), 0, st, A);
   return hipGetLastError();
 }

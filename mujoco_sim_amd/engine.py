@@ -31,7 +31,7 @@ class Model:
 
     def __getattr__(self, name):
         c = self.__dict__.get("c")
-        if c is not None and name in capi._INT_SIZES + capi._INT_SIZES2 + capi._INT_SIZES4 + capi._INT_SIZES6 + ["meaninertia", "opt"]:
+        if c is not None and name in capi._INT_SIZES + capi._INT_SIZES2 + capi._INT_SIZES4 + capi._INT_SIZES6 + capi._INT_SIZES7 + ["meaninertia", "opt"]:
             return getattr(c, name)
         raise AttributeError(name)
 
@@ -327,6 +327,16 @@ class Engine:
     @ray_mesh_mode.setter
     def ray_mesh_mode(self, mode):
         _chk(self.lib, self.lib.mjh_ray_set_mesh_mode(self.h, int(mode)), "mjh_ray_set_mesh_mode")
+
+    @property
+    def ray_mesh_surface(self):
+        """what a visible mesh geom is to a ray: 0 (default) its convex hull, 1 the mesh's own triangles where the asset has any
+        (mjh_ray_set_mesh_surface); rays and depth images both obey it"""
+        return self.lib.mjh_ray_get_mesh_surface(self.h)
+
+    @ray_mesh_surface.setter
+    def ray_mesh_surface(self, surface):
+        _chk(self.lib, self.lib.mjh_ray_set_mesh_surface(self.h, int(surface)), "mjh_ray_set_mesh_surface")
 
     def ray(self, pnt, vec, env0=0, n=None, **options):
         """rays pnt + x vec against the geoms of envs [env0, env0 + n): [nray, 3] arrays are one ray set shared by all envs, [n, nray, 3]
