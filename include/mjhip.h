@@ -185,6 +185,11 @@ typedef struct mjh_model {
   int nmeshtri;
   int *mesh_triadr, *mesh_trinum;   /* [nmesh] */
   double* mesh_tri;                 /* [9*nmeshtri]: a, b, c per triangle, in the frame of mesh_vert */
+  /* ---- appended for colour images (older fields keep their offsets) ----
+   * <geom rgba> (its own, its default class's, or its <material>'s): mjh_render shades with r, g, b; the alpha is carried and not
+   * used.  0.5 0.5 0.5 1 unless set [UPSTREAM, unverified here: MuJoCo's geom default].  NULL in a model assembled from tables: every
+   * geom has the default. */
+  double* geom_rgba;                /* [4*ngeom] */
 } mjh_model;
 
 /* ------------------------------------------------- model builder (host) */
@@ -246,6 +251,9 @@ int mjh_builder_add_sensor(mjh_builder*, const char* name, int type /* mjh_senso
 /* <camera> (fixed mode): returns the camera id.  pos / quat NULL: the identity (quat is normalised); fovy <= 0: MuJoCo's default of 45
  * degrees; fovy >= 180 or a bad body: MJH_ERR_ARG */
 int mjh_builder_add_camera(mjh_builder*, const char* name, int body, const double pos[3], const double quat[4], double fovy);
+/* <geom rgba>: the colour of geom `geom` (the id an mjh_builder_add_*geom call returned; the compiled model may number it differently,
+ * the colour follows it).  A bad id, a NULL pointer or a component outside [0, 1]: MJH_ERR_ARG, nothing is changed. */
+int mjh_builder_set_geom_rgba(mjh_builder*, int geom, const double rgba[4]);
 /* compile: derives inertias, qpos0, invweight0, meaninertia, rbound, pair list */
 mjh_model* mjh_builder_compile(mjh_builder*);
 void mjh_model_destroy(mjh_model*);
@@ -539,6 +547,37 @@ void mjh_depth_default_options(mjh_depth_options*);   /* 0, 64, 64, -1, 1, 0, 1,
 int mjh_depth_device(mjh_engine*, int env0, int n, const mjh_depth_options*, float* d_depth /*[n][height][width]*/, int* d_geomid);
 /* host pointers (fp32 images; geomid may be NULL): calls the device form through an engine-owned staging buffer and synchronises */
 int mjh_depth(mjh_engine*, int env0, int n, const mjh_depth_options*, float* depth, int* geomid);
+
+/* RGB-D images: beside mjh_depth's depth and geom id, the world-frame surface normal at every pixel's hit and a shaded colour image.
+ * Two launches on the engine's stream: the depth launch exactly as mjh_depth_device issues it (so depth and geomid are mjh_depth's
+ * bits), then a shading kernel that reads those two images, regenerates each pixel's ray and resolves the normal on the one geom
+ * the pixel names.
+ *   normal: the unit normal of the surface the ray hits, oriented towards the ray's origin (n . v <= 0: a camera inside a sphere gets
+ *   the inward normal of the far surface; two-sided surfaces need no convention); a miss is (0, 0, 0).  In the geom's frame, at the
+ *   hit point h, before orientation: plane (0, 0, 1); sphere h / |h|; ellipsoid (h_x / a^2, h_y / b^2, h_z / c^2) normalised; capsule
+ *   h - (0, 0, clamp(h_z, -s1, s1)) normalised; cylinder the cap (0, 0, sign h_z) where |h_z| - s1 >= hypot(h_x, h_y) - s0, else radial;
+ *   box the axis with the largest |h_i| - s_i, sign of h_i; height field the geometric normal of the top triangle the ray hit, or
+ *   the wall's, or the base's; mesh as its hull: the hull plane with the largest n . h - d; mesh as its triangles: e1 x e2 of the
+ *   triangle the ray hit.  On an exact tie between two features of one geom (a crease) either feature's normal is right.
+ *   rgba: four bytes per pixel, R, G, B, A in memory order.  On a hit channel c of R, G, B is (int)(255 min(1, geom_rgba[g][c] shade)
+ *   + 0.5) in fp32 with shade = ambient + diffuse |n . v^| (v^: the unit ray direction), and A is 255: the geom's own alpha is not
+ *   used, there is no transparency.  On a miss all four channels are (int)(255 background[c] + 0.5).
+ * Any output may be NULL, not all four; with normal and rgba both NULL the call is mjh_depth_device.  Errors are mjh_depth's; in
+ * addition ambient or diffuse negative or not finite, or a background component outside [0, 1], return MJH_ERR_ARG.  An error launches
+ * nothing and writes nothing.  Call-sequence rules, mesh mode, mesh surface, slot masks, per-env sizes and "nothing of the state is
+ * written" are mjh_depth's.  The colour table is uploaded with the other ray tables at the engine's first render call. */
+typedef struct mjh_render_options {
+  mjh_depth_options view;   /* camera, size, bodyexclude, flg_static, range, cull, cutoff: exactly mjh_depth's */
+  float ambient, diffuse;   /* shade = ambient + diffuse * |n . v^|   (defaults 0.3, 0.7: a face-on surface shows its own rgba) */
+  float background[4];      /* colour of a miss, components in [0,1] (default 0 0 0 0) */
+} mjh_render_options;
+void mjh_render_default_options(mjh_render_options*);
+/* device pointers; enqueued on the engine's stream, no synchronisation.  An image the caller does not take (NULL) but the shading
+ * needs lives in engine-owned scratch.  options may be NULL (the defaults) */
+int mjh_render_device(mjh_engine*, int env0, int n, const mjh_render_options*,
+                      float* d_depth, int* d_geomid, float* d_normal /*[n][H][W][3]*/, unsigned char* d_rgba /*[n][H][W][4]*/);
+/* host pointers: calls the device form through the engine-owned staging buffer and synchronises */
+int mjh_render(mjh_engine*, int env0, int n, const mjh_render_options*, float* depth, int* geomid, float* normal, unsigned char* rgba);
 
 /* zero-copy export for the single ROS state topic: packs time(1)+qpos(nq)+qvel(nv)
  * fp32 per env into a caller-provided DEVICE buffer [nenv*(1+nq+nv)] on the engine's

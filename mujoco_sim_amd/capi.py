@@ -85,6 +85,8 @@ _ARRAYS6 = [("cam_bodyid", "i", "ncam"), ("cam_pos", "d", "3*ncam"), ("cam_quat"
 # appended for rays against a mesh's own triangles (behind cam_names)
 _INT_SIZES7 = ["nmeshtri"]
 _ARRAYS7 = [("mesh_triadr", "i", "nmesh"), ("mesh_trinum", "i", "nmesh"), ("mesh_tri", "d", "9*nmeshtri")]
+# appended for colour images (behind mesh_tri)
+_ARRAYS8 = [("geom_rgba", "d", "4*ngeom")]
 
 
 class Model(C.Structure):
@@ -108,13 +110,14 @@ class Model(C.Structure):
         + [("cam_names", C.POINTER(C.c_char_p))]
         + [(n, C.c_int) for n in _INT_SIZES7]
         + [(n, c_int_p if t == "i" else c_double_p) for n, t, _ in _ARRAYS7]
+        + [(n, c_int_p if t == "i" else c_double_p) for n, t, _ in _ARRAYS8]
     )
 
     def array(self, name):
         """numpy copy of a model array."""
         import numpy as np
 
-        for n, t, expr in _ARRAYS + _ARRAYS2 + _ARRAYS3 + _ARRAYS4 + _ARRAYS5 + _ARRAYS6 + _ARRAYS7:
+        for n, t, expr in _ARRAYS + _ARRAYS2 + _ARRAYS3 + _ARRAYS4 + _ARRAYS5 + _ARRAYS6 + _ARRAYS7 + _ARRAYS8:
             if n == name:
                 ln = eval(expr, {}, {k: getattr(self, k) for k in _INT_SIZES + _INT_SIZES2 + _INT_SIZES4 + _INT_SIZES5 + _INT_SIZES6 + _INT_SIZES7})
                 ptr = getattr(self, n)
@@ -137,6 +140,9 @@ class RayOptions(C.Structure):
 class DepthOptions(C.Structure):
     _fields_ = [("camera", C.c_int), ("width", C.c_int), ("height", C.c_int), ("bodyexclude", C.c_int), ("flg_static", C.c_int),
                 ("range", C.c_int), ("cull", C.c_int), ("cutoff", C.c_double)]
+
+class RenderOptions(C.Structure):
+    _fields_ = [("view", DepthOptions), ("ambient", C.c_float), ("diffuse", C.c_float), ("background", C.c_float * 4)]
 
 
 # every symbol include/mjhip.h declares: (name, restype, argtypes)
@@ -169,6 +175,7 @@ SYMBOLS = [
     ("mjh_builder_set_mocap", C.c_int, [_vp, C.c_int]),
     ("mjh_builder_add_site", C.c_int, [_vp, C.c_char_p, C.c_int, c_double_p, c_double_p]),
     ("mjh_builder_add_camera", C.c_int, [_vp, C.c_char_p, C.c_int, c_double_p, c_double_p, C.c_double]),
+    ("mjh_builder_set_geom_rgba", C.c_int, [_vp, C.c_int, c_double_p]),
     ("mjh_builder_add_sensor", C.c_int, [_vp, C.c_char_p, C.c_int, C.c_int]),
     ("mjh_builder_compile", Model_p, [_vp]),
     ("mjh_model_destroy", None, [Model_p]),
@@ -240,6 +247,9 @@ SYMBOLS = [
     ("mjh_depth_default_options", None, [C.POINTER(DepthOptions)]),
     ("mjh_depth", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(DepthOptions), _vp, _vp]),
     ("mjh_depth_device", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(DepthOptions), _vp, _vp]),
+    ("mjh_render_default_options", None, [C.POINTER(RenderOptions)]),
+    ("mjh_render", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(RenderOptions), _vp, _vp, _vp, _vp]),
+    ("mjh_render_device", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(RenderOptions), _vp, _vp, _vp, _vp]),
     ("mjh_export_state_device", C.c_int, [_vp, _vp]),
     ("mjh_state_stride", C.c_int, [_vp]),
     ("mjh_mirror_create", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(_vp)]),

@@ -17,6 +17,7 @@
 #include "step_kernel.h"
 #include "dev_ray.h"
 #include "dev_depth.h"
+#include "dev_render.h"
 
 void mjh_set_error(const std::string& s);  // model_builder.cpp
 hipError_t mjh_launch_window(hipStream_t st, int nvt, int grid, size_t lds, const DConst* dC, const DState& S, int env0, int n, int nl, int wxf, int n32, int n64);   // window.hip
@@ -123,6 +124,9 @@ struct mjh_engine {
   int ray_mesh_surface = 0; bool ray_tri_ready = false; std::vector<int4> ray_gi_mesh_host;
   int4* ray_ginfo_tri = nullptr; RayTriMesh* ray_trimesh = nullptr; RayNode* ray_nodes = nullptr; float4* ray_tris = nullptr;
   float* ray_io = nullptr; size_t ray_io_floats = 0;
+  // colour images (mjh_render / mjh_render_device, render.hip): geom_rgba as float4 per geom, uploaded at the first render call; the depth
+  // and geom-id images of a device-form call whose caller takes neither
+  float4* ray_color = nullptr; float* render_io = nullptr; size_t render_io_floats = 0;
 };
 
 static int pad32(int n) { return ((n + 31) / 32) * 32; }
@@ -797,6 +801,7 @@ extern "C" void mjh_destroy(mjh_engine* e) {
   for (void* p : e->allocs) (void)hipFree(p);
   if (e->scratch) (void)hipFree(e->scratch);
   if (e->ray_io) (void)hipFree(e->ray_io);
+  if (e->render_io) (void)hipFree(e->render_io);
   if (e->h_dense) (void)hipHostFree(e->h_dense);
   if (e->h_wn) (void)hipHostFree(e->h_wn);
   if (e->h_io) (void)hipHostFree(e->h_io);
@@ -2021,14 +2026,16 @@ static int ray_scene(mjh_engine* e, int env0, int n, bool bodies, int bodyexclud
   W->bodyexclude = bodyexclude; W->flg_static = flg_static ? 1 : 0; W->cutoff = cutoff > 0 ? (float)cutoff : 0.0f;
   return MJH_OK;
 }
-// the device staging buffer of mjh_ray and mjh_depth, grown to `need` floats
-static int ray_io_reserve(mjh_engine* e, size_t need) {
-  if (need <= e->ray_io_floats) return MJH_OK;
-  if (e->ray_io) { HIPCHK(hipStreamSynchronize(e->stream)); HIPCHK(hipFree(e->ray_io)); e->ray_io = nullptr; e->ray_io_floats = 0; }
-  HIPCHK(hipMalloc((void**)&e->ray_io, need * sizeof(float)));
-  e->ray_io_floats = need;
+// an engine-owned device buffer grown to `need` floats (the stream is drained before a buffer it may still use is freed)
+static int io_reserve(mjh_engine* e, float** buf, size_t* have, size_t need) {
+  if (need <= *have) return MJH_OK;
+  if (*buf) { HIPCHK(hipStreamSynchronize(e->stream)); HIPCHK(hipFree(*buf)); *buf = nullptr; *have = 0; }
+  HIPCHK(hipMalloc((void**)buf, need * sizeof(float)));
+  *have = need;
   return MJH_OK;
 }
+// the device staging buffer of mjh_ray, mjh_depth and mjh_render
+static int ray_io_reserve(mjh_engine* e, size_t need) { return io_reserve(e, &e->ray_io, &e->ray_io_floats, need); }
 extern "C" int mjh_ray_device(mjh_engine* e, int env0, int n, int nray, const float* d_pnt, const float* d_vec, const mjh_ray_options* opt,
                               float* d_dist, int* d_geomid) {
   ENG(e);
@@ -2083,14 +2090,27 @@ extern "C" void mjh_depth_default_options(mjh_depth_options* o) {
   o->camera = 0; o->width = 64; o->height = 64; o->bodyexclude = -1; o->flg_static = 1; o->range = 0; o->cull = 1; o->cutoff = 0.0;
 }
 // argument checks shared by both entry points: nothing is launched when one fails
-static int depth_check(const mjh_engine* e, int env0, int n, const mjh_depth_options& o, const void* depth) {
+static int depth_check(const mjh_engine* e, int env0, int n, const mjh_depth_options& o, const void* depth, bool need_depth = true) {
   const mjh_model* m = e->model;
   if (m->ncam <= 0) { mjh_set_error("mjh_depth: the model has no camera"); return MJH_ERR_ARG; }
   if (o.camera < 0 || o.camera >= m->ncam) { mjh_set_error("mjh_depth: camera id out of range"); return MJH_ERR_ARG; }
   if (o.bodyexclude < -1 || o.bodyexclude >= m->nbody) { mjh_set_error("mjh_depth: bodyexclude out of range"); return MJH_ERR_ARG; }
   if (env0 < 0 || n <= 0 || env0 + n > e->nenv) { mjh_set_error("mjh_depth: env range out of bounds"); return MJH_ERR_ARG; }
   if (o.width <= 0 || o.height <= 0 || (long long)o.width * o.height * n > 0x3fffffffLL) { mjh_set_error("mjh_depth: width and height must be positive (and n * width * height below 2^30)"); return MJH_ERR_ARG; }
-  if (!depth) { mjh_set_error("mjh_depth: null pointer"); return MJH_ERR_ARG; }
+  if (need_depth && !depth) { mjh_set_error("mjh_depth: null pointer"); return MJH_ERR_ARG; }
+  return MJH_OK;
+}
+// ray_scene() and the depth launch's descriptor (checked options): what mjh_depth_device and mjh_render_device hand to mjh_launch_depth
+static int depth_chain(mjh_engine* e, int env0, int n, const mjh_depth_options& o, float* d_depth, int* d_geomid, DepthArgs* A) {
+  const mjh_model* m = e->model;
+  int rc = ray_scene(e, env0, n, true, o.bodyexclude, o.flg_static, o.cutoff, &A->W, &A->T);
+  if (rc) return rc;
+  A->depth = d_depth; A->geomid = d_geomid;
+  A->width = o.width; A->height = o.height; A->range = o.range ? 1 : 0; A->cull = o.cull ? 1 : 0;
+  A->cam_body = m->cam_bodyid[o.camera];
+  for (int k = 0; k < 3; k++) A->cam_pos[k] = (float)m->cam_pos[3 * o.camera + k];
+  for (int k = 0; k < 4; k++) A->cam_quat[k] = (float)m->cam_quat[4 * o.camera + k];
+  A->scale = (float)(std::tan(0.5 * m->cam_fovy[o.camera] * 3.14159265358979323846 / 180.0) / (double)o.height);
   return MJH_OK;
 }
 extern "C" int mjh_depth_device(mjh_engine* e, int env0, int n, const mjh_depth_options* opt, float* d_depth, int* d_geomid) {
@@ -2099,16 +2119,9 @@ extern "C" int mjh_depth_device(mjh_engine* e, int env0, int n, const mjh_depth_
   if (opt) o = *opt;
   int rc = depth_check(e, env0, n, o, d_depth);
   if (rc) return rc;
-  const mjh_model* m = e->model;
   DepthArgs A{};
-  rc = ray_scene(e, env0, n, true, o.bodyexclude, o.flg_static, o.cutoff, &A.W, &A.T);
+  rc = depth_chain(e, env0, n, o, d_depth, d_geomid, &A);
   if (rc) return rc;
-  A.depth = d_depth; A.geomid = d_geomid;
-  A.width = o.width; A.height = o.height; A.range = o.range ? 1 : 0; A.cull = o.cull ? 1 : 0;
-  A.cam_body = m->cam_bodyid[o.camera];
-  for (int k = 0; k < 3; k++) A.cam_pos[k] = (float)m->cam_pos[3 * o.camera + k];
-  for (int k = 0; k < 4; k++) A.cam_quat[k] = (float)m->cam_quat[4 * o.camera + k];
-  A.scale = (float)(std::tan(0.5 * m->cam_fovy[o.camera] * 3.14159265358979323846 / 180.0) / (double)o.height);
   HIPCHK(mjh_launch_depth(e->stream, A));
   return MJH_OK;
 }
@@ -2126,6 +2139,81 @@ extern "C" int mjh_depth(mjh_engine* e, int env0, int n, const mjh_depth_options
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(depth, d_depth, nout * sizeof(float), hipMemcpyDeviceToHost, e->stream));
   if (geomid) HIPCHK(hipMemcpyAsync(geomid, d_gid, nout * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return MJH_OK;
+}
+
+// ---- RGB-D images (mjh_render / mjh_render_device, render.hip): the depth launch exactly as mjh_depth_device issues it — into the
+// caller's buffers, or into engine-owned scratch where the caller takes neither image — then mjh_shade_kernel on the same stream.
+extern "C" void mjh_render_default_options(mjh_render_options* o) {
+  if (!o) return;
+  mjh_depth_default_options(&o->view);
+  o->ambient = 0.3f; o->diffuse = 0.7f;
+  for (int k = 0; k < 4; k++) o->background[k] = 0.0f;
+}
+// argument checks shared by both entry points: nothing is launched when one fails
+static int render_check(const mjh_engine* e, int env0, int n, const mjh_render_options& o, const void* depth, const void* geomid, const void* normal, const void* rgba) {
+  if (!depth && !geomid && !normal && !rgba) { mjh_set_error("mjh_render: every output pointer is null"); return MJH_ERR_ARG; }
+  if (!(o.ambient >= 0.0f && std::isfinite(o.ambient) && o.diffuse >= 0.0f && std::isfinite(o.diffuse))) { mjh_set_error("mjh_render: ambient and diffuse must be finite and not negative"); return MJH_ERR_ARG; }
+  for (int k = 0; k < 4; k++) if (!(o.background[k] >= 0.0f && o.background[k] <= 1.0f)) { mjh_set_error("mjh_render: background components must lie in [0, 1]"); return MJH_ERR_ARG; }
+  return depth_check(e, env0, n, o.view, depth, !(normal || rgba));      // (with a normal or colour image the depth image is optional)
+}
+static int render_tables(mjh_engine* e) {
+  if (e->ray_color) return MJH_OK;
+  const mjh_model* m = e->model;
+  std::vector<float4> col((size_t)std::max(m->ngeom, 1), make_float4(0.5f, 0.5f, 0.5f, 1.0f));      // (a model assembled from tables has no geom_rgba: the default)
+  if (m->geom_rgba) for (int g = 0; g < m->ngeom; g++) col[g] = make_float4((float)m->geom_rgba[4*g], (float)m->geom_rgba[4*g+1], (float)m->geom_rgba[4*g+2], (float)m->geom_rgba[4*g+3]);
+  float4* d = nullptr;
+  int rc = dev_alloc(e, &d, col.size(), false);
+  if (rc) return rc;
+  HIPCHK(hipMemcpy(d, col.data(), col.size() * sizeof(float4), hipMemcpyHostToDevice));
+  e->ray_color = d;
+  return MJH_OK;
+}
+extern "C" int mjh_render_device(mjh_engine* e, int env0, int n, const mjh_render_options* opt, float* d_depth, int* d_geomid, float* d_normal, unsigned char* d_rgba) {
+  ENG(e);
+  mjh_render_options o; mjh_render_default_options(&o);
+  if (opt) o = *opt;
+  int rc = render_check(e, env0, n, o, d_depth, d_geomid, d_normal, d_rgba);
+  if (rc) return rc;
+  if (!d_normal && !d_rgba) return mjh_depth_device(e, env0, n, &o.view, d_depth, d_geomid);
+  rc = render_tables(e);
+  if (rc) return rc;
+  const size_t nout = (size_t)n * o.view.width * o.view.height;
+  if (!d_depth || !d_geomid) {
+    rc = io_reserve(e, &e->render_io, &e->render_io_floats, 2 * nout);
+    if (rc) return rc;
+    if (!d_depth) d_depth = e->render_io;
+    if (!d_geomid) d_geomid = (int*)(e->render_io + nout);
+  }
+  ShadeArgs A{};
+  rc = depth_chain(e, env0, n, o.view, d_depth, d_geomid, &A.D);
+  if (rc) return rc;
+  HIPCHK(mjh_launch_depth(e->stream, A.D));
+  A.color = e->ray_color; A.normal = d_normal; A.rgba = (unsigned*)d_rgba;
+  A.ambient = o.ambient; A.diffuse = o.diffuse;
+  A.background = render_pack(o.background[0], o.background[1], o.background[2], o.background[3]);
+  HIPCHK(mjh_launch_shade(e->stream, A));
+  return MJH_OK;
+}
+extern "C" int mjh_render(mjh_engine* e, int env0, int n, const mjh_render_options* opt, float* depth, int* geomid, float* normal, unsigned char* rgba) {
+  ENG(e);
+  mjh_render_options o; mjh_render_default_options(&o);
+  if (opt) o = *opt;
+  int rc = render_check(e, env0, n, o, depth, geomid, normal, rgba);
+  if (rc) return rc;
+  if (!normal && !rgba) return mjh_depth(e, env0, n, &o.view, depth, geomid);
+  const size_t nout = (size_t)n * o.view.width * o.view.height;
+  rc = ray_io_reserve(e, 6 * nout);
+  if (rc) return rc;
+  float* const d_depth = e->ray_io; int* const d_gid = (int*)(e->ray_io + nout); float* const d_normal = e->ray_io + 2 * nout;
+  unsigned char* const d_rgba = (unsigned char*)(e->ray_io + 5 * nout);
+  rc = mjh_render_device(e, env0, n, &o, d_depth, d_gid, normal ? d_normal : nullptr, rgba ? d_rgba : nullptr);
+  if (rc) return rc;
+  if (depth) HIPCHK(hipMemcpyAsync(depth, d_depth, nout * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+  if (geomid) HIPCHK(hipMemcpyAsync(geomid, d_gid, nout * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  if (normal) HIPCHK(hipMemcpyAsync(normal, d_normal, 3 * nout * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+  if (rgba) HIPCHK(hipMemcpyAsync(rgba, d_rgba, nout * sizeof(unsigned), hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   return MJH_OK;
 }

@@ -119,6 +119,7 @@ struct Loader {
   double bmass = 0, binertia = 0;   // <compiler boundmass boundinertia>, raised to the process-wide floor of mjh_load_set_bounds
   Defaults def;
   std::map<std::string, int> body_id, joint_id, mesh_id, site_id, hfield_id;
+  std::map<std::string, std::array<double, 4>> material_rgba;   // <asset><material name rgba>: colour only, per file like the meshes
   std::vector<int> body_parent;      // parent body of every body added so far
   // <default class="..."> tables: class -> element tag -> attributes (a nested class starts from its parent's); the
   // unnamed top-level <default> is class "main".  An element takes the attributes it does not set itself from its class
@@ -203,18 +204,31 @@ struct Loader {
     if (nums(n.get("contype"), &v, 1)) contype = (int)v;
     if (nums(n.get("conaffinity"), &v, 1)) conaff = (int)v;
     if (nums(n.get("density"), &v, 1)) density = v;
+    // colour: the geom's own rgba (or its class's), else its material's, else the builder's default
+    // [UPSTREAM, unverified here] a geom's own rgba takes precedence over its material's
+    double rgba[4]; bool coloured = false;
+    // (a colour that is not four numbers in [0, 1] is dropped with a note: such a file loaded before colours were read)
+    auto usable = [](const double* c) { for (int k = 0; k < 4; k++) if (!(c[k] >= 0.0 && c[k] <= 1.0)) return false; return true; };
+    if (n.get("rgba")) {
+      if (nums(n.get("rgba"), rgba, 4) == 4 && usable(rgba)) coloured = true;
+      else note += std::string("ignored geom rgba \"") + n.get("rgba") + "\" (not four numbers in [0, 1]: default colour); ";
+    } else if (const char* mat = n.get("material")) {
+      auto it = material_rgba.find(mat);
+      if (it == material_rgba.end()) note += std::string("geom material ") + mat + " not found (default colour); ";
+      else { std::memcpy(rgba, it->second.data(), sizeof rgba); coloured = true; }
+    }
+    int gid;
     if (gt == MJH_GEOM_MESH) {
       auto it = mesh_id.find(n.get("mesh") ? n.get("mesh") : "");
       if (it == mesh_id.end()) { note += std::string("skipped mesh geom (mesh ") + (n.get("mesh") ? n.get("mesh") : "?") + " not loaded); "; return true; }
-      mjh_builder_add_mesh_geom(b, n.get("name"), body, it->second, pos, quat, fr, condim, contype, conaff, density);
-      return true;
-    }
-    if (gt == MJH_GEOM_HFIELD) {      // (the geom's size is ignored: the asset's size sets the terrain)
+      gid = mjh_builder_add_mesh_geom(b, n.get("name"), body, it->second, pos, quat, fr, condim, contype, conaff, density);
+    } else if (gt == MJH_GEOM_HFIELD) {      // (the geom's size is ignored: the asset's size sets the terrain)
       auto it = hfield_id.find(n.get("hfield") ? n.get("hfield") : "");
       if (it == hfield_id.end()) { note += std::string("skipped hfield geom (hfield ") + (n.get("hfield") ? n.get("hfield") : "?") + " not loaded); "; return true; }
-      return mjh_builder_add_hfield_geom(b, n.get("name"), body, it->second, pos, quat, fr, condim, contype, conaff) >= 0;
-    }
-    mjh_builder_add_geom(b, n.get("name"), body, gt, size, pos, quat, fr, condim, contype, conaff, density);
+      gid = mjh_builder_add_hfield_geom(b, n.get("name"), body, it->second, pos, quat, fr, condim, contype, conaff);
+      if (gid < 0) return false;
+    } else gid = mjh_builder_add_geom(b, n.get("name"), body, gt, size, pos, quat, fr, condim, contype, conaff, density);
+    if (coloured && gid >= 0 && mjh_builder_set_geom_rgba(b, gid, rgba) < 0) return false;
     return true;
   }
   bool joint(const Node& n0, int body, bool freejoint) {
@@ -340,7 +354,7 @@ struct Loader {
     if (root.tag != "mujoco") { mjh_set_error("root element must be <mujoco>"); return false; }
     if (first) b = mjh_builder_create();
     robot_file = !first;      // files after the world file are robots (MjSim::init composition)
-    degree = true; autolimits = false; def = Defaults(); basedir = dir; meshdir.clear(); mesh_id.clear(); hfield_id.clear(); classes.clear(); childclass.clear();
+    degree = true; autolimits = false; def = Defaults(); basedir = dir; meshdir.clear(); mesh_id.clear(); hfield_id.clear(); material_rgba.clear(); classes.clear(); childclass.clear();
     mjh_option o; mjh_builder_get_option(b, &o);
     bool solver_named = false;
     // first pass: compiler / option / default (they may appear after worldbody in a file)
@@ -450,6 +464,23 @@ struct Loader {
       const int id = mjh_builder_add_hfield(b, name.c_str(), nrow, ncol, size, elev.empty() ? nullptr : elev.data());
       if (id < 0) { mjh_set_error("hfield " + name + ": " + mjh_last_error()); return false; }
       hfield_id[name] = id;
+    }
+    // <asset><material name rgba>: the colour a geom with material= takes unless it has an rgba of its own; a material without rgba is
+    // white [UPSTREAM, unverified here: MuJoCo's material default is 1 1 1 1]
+    for (auto& c : root.kids) if (c->tag == "asset") for (auto& a : c->kids) if (a->tag == "material") {
+      const Node mn = with_defaults(*a);
+      if (!mn.get("name")) { note += "skipped <material> without name; "; continue; }
+      std::array<double, 4> col = {1, 1, 1, 1};
+      if (mn.get("rgba")) {
+        std::array<double, 4> c = {1, 1, 1, 1};
+        bool ok = nums(mn.get("rgba"), c.data(), 4) == 4;
+        for (int k = 0; k < 4; k++) ok = ok && c[k] >= 0.0 && c[k] <= 1.0;
+        if (ok) col = c;
+        else note += std::string("ignored rgba of material ") + mn.get("name") + " (not four numbers in [0, 1]: white); ";
+      }
+      for (auto& at : mn.attr) if (at.first != "name" && at.first != "rgba" && at.first != "class")
+        note += "ignored material attribute " + at.first + " of " + mn.get("name") + " (colour only); ";
+      material_rgba[mn.get("name")] = col;
     }
     const int body_first = std::max(1, (int)body_parent.size());      // first body this file adds
     for (auto& c : root.kids) if (c->tag == "worldbody") if (!children(*c, 0)) return false;

@@ -32,6 +32,7 @@ struct BJoint {
 struct BGeom {
   std::string name; int body, type; double size[3], pos[3], quat[4], friction[3];
   int condim, contype, conaffinity; double density; int mesh = -1; int hfield = -1;
+  double rgba[4] = {0.5, 0.5, 0.5, 1.0};      // [UPSTREAM, unverified here] MuJoCo's geom default
 };
 // height field asset: elevation grid as given (normalised at compile time)
 struct BHField { std::string name; int nrow, ncol; double size[4]; std::vector<double> data; };
@@ -579,6 +580,12 @@ extern "C" int mjh_builder_add_camera(mjh_builder* b, const char* name, int body
   if (quat) { for (int i = 0; i < 4; i++) x.quat[i] = quat[i]; hm::normalize4(x.quat); } else { x.quat[0] = 1; x.quat[1] = x.quat[2] = x.quat[3] = 0; }
   b->cameras.push_back(x); return (int)b->cameras.size() - 1;
 }
+extern "C" int mjh_builder_set_geom_rgba(mjh_builder* b, int geom, const double rgba[4]) {
+  if (!b || geom < 0 || geom >= (int)b->geoms.size() || !rgba) { g_err = "set_geom_rgba: bad geom"; return MJH_ERR_ARG; }
+  for (int i = 0; i < 4; i++) if (!(rgba[i] >= 0.0 && rgba[i] <= 1.0)) { g_err = "set_geom_rgba: components must lie in [0, 1]"; return MJH_ERR_ARG; }
+  for (int i = 0; i < 4; i++) b->geoms[geom].rgba[i] = rgba[i];
+  return MJH_OK;
+}
 extern "C" int mjh_builder_add_sensor(mjh_builder* b, const char* name, int type, int site) {
   if (site < 0 || site >= (int)b->sites.size()) { g_err = "add_sensor: bad site"; return MJH_ERR_ARG; }
   if (type != MJH_SENS_FORCE && type != MJH_SENS_TORQUE) { g_err = "add_sensor: only force and torque sensors are implemented (the types MjSim::init_sensors accepts)"; return MJH_ERR_UNSUPPORTED; }
@@ -760,7 +767,7 @@ extern "C" mjh_model* mjh_builder_compile(mjh_builder* B) {
   // geoms
   std::vector<int> geom_type(ngeom), geom_bodyid(ngeom), geom_condim(ngeom), geom_contype(ngeom), geom_conaffinity(ngeom), geom_priority(ngeom);
   std::vector<double> geom_pos(3*ngeom), geom_quat(4*ngeom), geom_size(3*ngeom), geom_rb(ngeom), geom_friction(3*ngeom),
-      geom_solmix(ngeom), geom_solref(2*ngeom), geom_solimp(5*ngeom), geom_margin(ngeom), geom_gap(ngeom);
+      geom_solmix(ngeom), geom_solref(2*ngeom), geom_solimp(5*ngeom), geom_margin(ngeom), geom_gap(ngeom), geom_rgba(4*ngeom);
   std::vector<std::string> geom_names(ngeom);
   std::vector<int> geom_dataid(ngeom, -1), mesh_vertadr, mesh_vertnum;
   std::vector<double> mesh_vert, mesh_plane;
@@ -780,7 +787,7 @@ extern "C" mjh_model* mjh_builder_compile(mjh_builder* B) {
     geom_names[g] = G.name; geom_type[g] = G.type; geom_bodyid[g] = newid[G.body];
     geom_condim[g] = G.condim; geom_contype[g] = G.contype; geom_conaffinity[g] = G.conaffinity; geom_priority[g] = 0;
     for (int k = 0; k < 3; k++) { geom_pos[3*g+k] = G.pos[k]; geom_size[3*g+k] = G.size[k]; geom_friction[3*g+k] = G.friction[k]; }
-    for (int k = 0; k < 4; k++) geom_quat[4*g+k] = G.quat[k];
+    for (int k = 0; k < 4; k++) { geom_quat[4*g+k] = G.quat[k]; geom_rgba[4*g+k] = G.rgba[k]; }
     geom_rb[g] = geom_rbound(G.type, G.size);
     geom_dataid[g] = G.type == MJH_GEOM_MESH ? G.mesh : -1;
     if (G.type == MJH_GEOM_HFIELD && G.hfield >= 0) {
@@ -1131,6 +1138,7 @@ extern "C" mjh_model* mjh_builder_compile(mjh_builder* B) {
   SETI(mesh_planeadr); SETI(mesh_planenum); SETI(mesh_plane);
   m->nmeshtri = (int)mesh_tri.size() / 9;
   SETI(mesh_triadr); SETI(mesh_trinum); SETI(mesh_tri);
+  SETI(geom_rgba);
 #undef SETI
   {   // height fields: elevation normalised to [0, 1] (minus the minimum, divided by the range when it is non-zero)
     const int nh = (int)B->hfields.size();
@@ -1268,6 +1276,7 @@ extern "C" mjh_model* mjh_model_replicate(const mjh_model* a, int G) {
   m->geom_priority = ialloc(NG); m->geom_dataid = ialloc(NG);
   m->geom_pos = dalloc((size_t)3*NG); m->geom_quat = dalloc((size_t)4*NG); m->geom_size = dalloc((size_t)3*NG); m->geom_rbound = dalloc(NG); m->geom_friction = dalloc((size_t)3*NG);
   m->geom_solmix = dalloc(NG); m->geom_solref = dalloc((size_t)2*NG); m->geom_solimp = dalloc((size_t)5*NG); m->geom_margin = dalloc(NG); m->geom_gap = dalloc(NG);
+  m->geom_rgba = dalloc((size_t)4*NG);
   for (int k = 0; k < G; k++) for (int g = 0; g < ng; g++) {
     if (k > 0 && a->body_weldid[a->geom_bodyid[g]] == 0) continue;
     const int G2 = gmap(k, g);
@@ -1275,7 +1284,7 @@ extern "C" mjh_model* mjh_model_replicate(const mjh_model* a, int G) {
     m->geom_contype[G2] = a->geom_contype[g]; m->geom_conaffinity[G2] = a->geom_conaffinity[g]; m->geom_priority[G2] = a->geom_priority[g];
     m->geom_dataid[G2] = a->geom_dataid ? a->geom_dataid[g] : -1;
     for (int q = 0; q < 3; q++) { m->geom_pos[3*G2+q] = a->geom_pos[3*g+q]; m->geom_size[3*G2+q] = a->geom_size[3*g+q]; m->geom_friction[3*G2+q] = a->geom_friction[3*g+q]; }
-    for (int q = 0; q < 4; q++) m->geom_quat[4*G2+q] = a->geom_quat[4*g+q];
+    for (int q = 0; q < 4; q++) { m->geom_quat[4*G2+q] = a->geom_quat[4*g+q]; m->geom_rgba[4*G2+q] = a->geom_rgba ? a->geom_rgba[4*g+q] : (q < 3 ? 0.5 : 1.0); }
     m->geom_rbound[G2] = a->geom_rbound[g]; m->geom_solmix[G2] = a->geom_solmix[g]; m->geom_margin[G2] = a->geom_margin[g]; m->geom_gap[G2] = a->geom_gap[g];
     for (int q = 0; q < 2; q++) m->geom_solref[2*G2+q] = a->geom_solref[2*g+q];
     for (int q = 0; q < 5; q++) m->geom_solimp[5*G2+q] = a->geom_solimp[5*g+q];
@@ -1325,7 +1334,7 @@ extern "C" void mjh_model_destroy(mjh_model* m) {
     m->site_bodyid, m->site_pos, m->site_quat, m->sensor_type, m->sensor_objid, m->sensor_adr, m->body_mocapid,
     m->hfield_nrow, m->hfield_ncol, m->hfield_adr, m->hfield_size, m->hfield_data,
     m->mesh_planeadr, m->mesh_planenum, m->mesh_plane, m->cam_bodyid, m->cam_pos, m->cam_quat, m->cam_fovy,
-    m->mesh_triadr, m->mesh_trinum, m->mesh_tri};
+    m->mesh_triadr, m->mesh_trinum, m->mesh_tri, m->geom_rgba};
   for (void* p : ptrs) std::free(p);
   auto freen = [](char** n, int c) { if (!n) return; for (int i = 0; i < c; i++) std::free(n[i]); std::free(n); };
   freen(m->body_names, m->nbody); freen(m->jnt_names, m->njnt); freen(m->geom_names, m->ngeom);

@@ -394,6 +394,47 @@ class Engine:
         o = self._depth_options(camera, width, height, options)
         _chk(self.lib, self.lib.mjh_depth_device(self.h, env0, n, C.byref(o), C.c_void_p(d_depth), C.c_void_p(d_geomid)), "mjh_depth_device")
 
+    # ---- RGB-D images: depth, geom id, world-frame normal, shaded colour
+    def _render_options(self, camera, width, height, options):
+        o = capi.RenderOptions()
+        self.lib.mjh_render_default_options(C.byref(o))
+        shading = {k: options.pop(k) for k in ("ambient", "diffuse", "background") if k in options}
+        o.view = self._depth_options(camera, width, height, options)
+        if "ambient" in shading:
+            o.ambient = float(shading["ambient"])
+        if "diffuse" in shading:
+            o.diffuse = float(shading["diffuse"])
+        if "background" in shading:
+            bg = [float(x) for x in shading["background"]]
+            if len(bg) != 4:
+                raise ValueError("background needs four components")
+            o.background = (C.c_float * 4)(*bg)
+        return o
+
+    def render(self, camera, width, height, env0=0, n=None, normal=True, rgba=True, **options):
+        """what camera `camera` (id or name) sees in envs [env0, env0 + n), with surface normals and colour.  options: mjh_depth_options'
+        and ambient, diffuse, background (mjh_render_options).  -> (depth [n, height, width] float32, geomid [n, height, width] int32,
+        normal [n, height, width, 3] float32 (world frame, towards the camera; None unless asked for), rgba [n, height, width, 4]
+        uint8 (None unless asked for)); a miss is (-1, -1, (0, 0, 0), background)"""
+        n = self.nenv - env0 if n is None else n
+        o = self._render_options(camera, width, height, dict(options))
+        shape = (max(n, 0), max(o.view.height, 0), max(o.view.width, 0))
+        depth = np.zeros(shape, dtype=np.float32); gid = np.zeros(shape, dtype=np.int32)
+        nrm = np.zeros(shape + (3,), dtype=np.float32) if normal else None
+        col = np.zeros(shape + (4,), dtype=np.uint8) if rgba else None
+        _chk(self.lib, self.lib.mjh_render(self.h, env0, n, C.byref(o), C.c_void_p(depth.ctypes.data), C.c_void_p(gid.ctypes.data),
+                                           C.c_void_p(nrm.ctypes.data) if normal else None, C.c_void_p(col.ctypes.data) if rgba else None), "mjh_render")
+        return depth, gid, nrm, col
+
+    def render_device(self, d_depth, d_geomid, d_normal, d_rgba, camera, width, height, env0=0, n=None, **options):
+        """mjh_render_device: device addresses (data_ptr()) of fp32 depth and int32 geomid [n, height, width], fp32 normal
+        [n, height, width, 3] and uint8 rgba [n, height, width, 4]; any may be None, not all; enqueued on the engine's stream, valid
+        after synchronize()"""
+        n = self.nenv - env0 if n is None else n
+        o = self._render_options(camera, width, height, dict(options))
+        _chk(self.lib, self.lib.mjh_render_device(self.h, env0, n, C.byref(o), C.c_void_p(d_depth), C.c_void_p(d_geomid),
+                                                  C.c_void_p(d_normal), C.c_void_p(d_rgba)), "mjh_render_device")
+
     def export_state_device(self, device_ptr):
         _chk(self.lib, self.lib.mjh_export_state_device(self.h, C.c_void_p(device_ptr)), "mjh_export_state_device")
 
