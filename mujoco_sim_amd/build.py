@@ -17,7 +17,7 @@ DENSE_HEADERS = ["dense_pgs.h"] + KERNEL_HEADERS
 WINDOW_HEADERS = ["window_kernel.h", "step_kernel.h", "patch_pgs.h", "window_pgs.h", "dev_math.h", "dev_collide.h", "dev_convex.h", "dev_types.h"]
 # source -> headers it includes (besides itself)
 SOURCES = {
-    "engine.hip": KERNEL_HEADERS + ["dev_ray.h", "ray_bvh.h", "dev_depth.h", "dev_render.h", API],
+    "engine.hip": KERNEL_HEADERS + ["dev_ray.h", "ray_bvh.h", "dev_depth.h", "dev_render.h", "ray_tables.h", API],
     "window.hip": WINDOW_HEADERS + [API],
     "dense.hip": DENSE_HEADERS + [API],
     "hfield.hip": KERNEL_HEADERS + [API],

@@ -194,7 +194,24 @@ RDEV float ray_hfield_height(const RayHField& H, const float* __restrict__ hd, f
   return h * H.size[2];
 }
 
-RDEV float ray_hfield(const float* p, const float* v, const RayHField& H, const float* __restrict__ hd) {
+// a candidate x of ray_hfield (the base, a wall, a top triangle) under ray_pick's rule.  NRM: where it replaces `best` (a strictly
+// smaller x, or the first one), its normal (nx, ny, nz) replaces nrm
+template <bool NRM>
+RDEV void ray_hfield_take(float& best, float x, float nx, float ny, float nz, float* nrm) {
+  if constexpr (NRM) {
+    const float nb = ray_pick(best, x);
+    if (nb != best) { best = nb; nrm[0] = nx; nrm[1] = ny; nrm[2] = nz; }
+  } else best = ray_pick(best, x);
+}
+
+// NRM: nrm also receives the normal of the feature that gives the returned x — the base (0, 0, -1), a wall's outward axis, or the
+// geometric normal of the top triangle: over cell (r, c) triangle k is z = z00 + u A + w B with u = (X + sx) / dx - c and
+// w = (Y + sy) / dy - r, so its upward normal is (-A / dx, -B / dy, 1) — in the geom frame, neither normalised nor oriented, (0, 0, 0)
+// without a hit.  The instance without NRM is the code as it was before the parameter existed, token for token: the kernels' bits
+// depend on it (HISTORY.md).
+template <bool NRM = false>
+RDEV float ray_hfield(const float* p, const float* v, const RayHField& H, const float* __restrict__ hd, float* nrm = nullptr) {
+  if constexpr (NRM) nrm[0] = nrm[1] = nrm[2] = 0.0f;
   const float sx = H.size[0], sy = H.size[1], sz = H.size[2], sb = H.size[3];
   const float bmin[3] = {-sx, -sy, -sb}, bmax[3] = {sx, sy, sz};
   float t0, t1;
@@ -204,7 +221,7 @@ RDEV float ray_hfield(const float* p, const float* v, const RayHField& H, const 
   // base
   if (v[2] != 0.0f) {
     const float x = (-sb - p[2]) / v[2];
-    if (fabsf(p[0] + x * v[0]) <= sx && fabsf(p[1] + x * v[1]) <= sy) best = ray_pick(best, x);
+    if (fabsf(p[0] + x * v[0]) <= sx && fabsf(p[1] + x * v[1]) <= sy) ray_hfield_take<NRM>(best, x, 0.0f, 0.0f, -1.0f, nrm);
   }
   // side walls, up to the terrain's edge
 #pragma unroll
@@ -217,7 +234,7 @@ RDEV float ray_hfield(const float* p, const float* v, const RayHField& H, const 
       const float o = ax ? p[0] + x * v[0] : p[1] + x * v[1], z = p[2] + x * v[2];
       if (x >= 0.0f && fabsf(o) <= so && z >= -sb) {
         const float h = ax ? ray_hfield_height(H, hd, o, w * sa) : ray_hfield_height(H, hd, w * sa, o);
-        if (z <= h) best = ray_pick(best, x);
+        if (z <= h) ray_hfield_take<NRM>(best, x, ax ? 0.0f : w, ax ? w : 0.0f, 0.0f, nrm);
       }
     }
   }
@@ -261,7 +278,7 @@ RDEV float ray_hfield(const float* p, const float* v, const RayHField& H, const 
         const float x = (z00 + u0 * A + w0 * B - p[2]) / den;
         const float u = (gu + x * ud) - (float)c, w = (gw + x * wd) - (float)r;
         const bool in = k ? (w >= u - (tolu + tolw) && u >= -tolu && w <= 1.0f + tolw) : (u >= w - (tolu + tolw) && w >= -tolw && u <= 1.0f + tolu);
-        if (in) best = ray_pick(best, x);
+        if (in) ray_hfield_take<NRM>(best, x, -A / dx, -B / dy, 1.0f, nrm);
       }
     }
   }
@@ -318,12 +335,18 @@ RDEV float ray_tri(const float* p, const float* v, float vn, float L, float sp, 
 // tests its triangles all the same: by the argument of ray_bvh.h it finds nothing below its bound there).  A node's slab test uses
 // the reciprocal direction (+-inf for a zero component: the products are then +-inf, or NaN for an origin on the slab's face, which
 // fminf / fmaxf drop: inside) and the box widened by sn = 3 sp.
-RDEV float ray_trimesh(const float* p, const float* v, const RayTriMesh& M, const RayNode* __restrict__ nodes, const float4* __restrict__ tris, float bound) {
+// NRM: nrm also receives e1 x e2 of the triangle the scan takes (the later one of the scan on an equal x) — the geom frame, neither
+// normalised nor oriented, (0, 0, 0) without a hit.  The shade kernel calls it on the one geom a pixel names with a bound a little above
+// the known x; there only the lanes that hold this geom are active: the ballot sees them alone, and every one of them stays in the scan
+// until it ends.  The instance without NRM is the code as it was before the parameter existed.
+template <bool NRM = false>
+RDEV float ray_trimesh(const float* p, const float* v, const RayTriMesh& M, const RayNode* __restrict__ nodes, const float4* __restrict__ tris, float bound, float* nrm = nullptr) {
   const float vn = fabsf(v[0]) + fabsf(v[1]) + fabsf(v[2]), pn = fabsf(p[0]) + fabsf(p[1]) + fabsf(p[2]);
   const float L = pn + M.r1, sp = RAY_SLACK * pn, sn = RAY_NODE_SLACK * sp;
   const float iv[3] = {1.0f / v[0], 1.0f / v[1], 1.0f / v[2]};
   const float pl[3] = {p[0] + sn, p[1] + sn, p[2] + sn}, ph[3] = {p[0] - sn, p[1] - sn, p[2] - sn};
   float cur = -1.0f, lim = bound;
+  if constexpr (NRM) nrm[0] = nrm[1] = nrm[2] = 0.0f;
   const int n = M.nnode;
   int i = 0;
   while (i < n) {
@@ -346,8 +369,12 @@ RDEV float ray_trimesh(const float* p, const float* v, const RayTriMesh& M, cons
       const float4* q = tris + (size_t)4 * (size_t)(leaf >> 3);
       const int cnt = leaf & 7;
       for (int t = 0; t < cnt; t++) {
-        const float x = ray_tri(p, v, vn, L, sp, q[4*t], q[4*t + 1], q[4*t + 2], q[4*t + 3]);
-        if (x >= 0.0f && x <= lim) { cur = x; lim = x; }
+        const float4 q1 = q[4*t + 1], q2 = q[4*t + 2];
+        const float x = ray_tri(p, v, vn, L, sp, q[4*t], q1, q2, q[4*t + 3]);
+        if (x >= 0.0f && x <= lim) {
+          cur = x; lim = x;
+          if constexpr (NRM) { nrm[0] = q1.y * q2.z - q1.z * q2.y; nrm[1] = q1.z * q2.x - q1.x * q2.z; nrm[2] = q1.x * q2.y - q1.y * q2.x; }
+        }
       }
     }
     i = i + 1;

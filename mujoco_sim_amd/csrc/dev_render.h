@@ -2,7 +2,9 @@
 // launch descriptor, the surface normal of every geom type a ray can see, resolved on the ONE geom a depth pixel names, and the colour
 // of a pixel.  The functions are __host__ __device__: tests/render_host builds them for the CPU and checks the very code the kernel
 // runs.  Nothing here walks an env's geoms: the depth launch has done that, the resolve functions take a geom, the ray in the geom's
-// frame and the ray parameter x of the hit, so ray.hip can take them later for mjh_ray.  gfx950 only.
+// frame and the ray parameter x of the hit, so ray.hip can take them later for mjh_ray.  The two table types whose normal needs a
+// scan — the height field and a mesh's triangles — have no code here: render_normal calls the NRM instances of dev_ray.h's ray_hfield
+// and ray_trimesh, the depth kernel's own walks, so the normal is that of the hit the depth kernel found.  gfx950 only.
 //
 // A normal is returned in the geom's frame, NOT normalised and NOT oriented (render_finish does both in the world frame).
 #pragma once
@@ -57,126 +59,8 @@ RDEV void normal_convex(const float* h, const float4* __restrict__ planes, int n
   }
 }
 
-// triangles (mesh surface 1): ray_trimesh's scan (dev_ray.h) that also keeps e1 x e2 of the triangle it takes — the later triangle of
-// the scan on an equal x, as there.  bound: a little above the known x of the hit, so subtrees the ray enters behind it are pruned.  The
-// return value is the x it found (-1: none: n stays 0).  In the kernel only the lanes that hold this geom are active: the ballot sees
-// them alone, and every one of them stays in the scan until it ends.
-RDEV float normal_trimesh(const float* p, const float* v, const RayTriMesh& M, const RayNode* __restrict__ nodes, const float4* __restrict__ tris, float bound, float* nrm) {
-  const float vn = fabsf(v[0]) + fabsf(v[1]) + fabsf(v[2]), pn = fabsf(p[0]) + fabsf(p[1]) + fabsf(p[2]);
-  const float L = pn + M.r1, sp = RAY_SLACK * pn, sn = RAY_NODE_SLACK * sp;
-  const float iv[3] = {1.0f / v[0], 1.0f / v[1], 1.0f / v[2]};
-  const float pl[3] = {p[0] + sn, p[1] + sn, p[2] + sn}, ph[3] = {p[0] - sn, p[1] - sn, p[2] - sn};
-  float cur = -1.0f, lim = bound;
-  nrm[0] = nrm[1] = nrm[2] = 0.0f;
-  const int n = M.nnode;
-  int i = 0;
-  while (i < n) {
-    const RayNode N = nodes[i];
-    float lo = -3.0e38f, hi = 3.0e38f;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      const float a = (N.bmin[k] - pl[k]) * iv[k], b = (N.bmax[k] - ph[k]) * iv[k];
-      lo = fmaxf(lo, fminf(a, b)); hi = fminf(hi, fmaxf(a, b));
-    }
-    const bool hit = lo <= hi && hi >= 0.0f && lo <= lim;
-#ifdef __HIP_DEVICE_COMPILE__
-    const bool go = __builtin_amdgcn_ballot_w64(hit) != 0;      // (uniform over the active lanes)
-#else
-    const bool go = hit;
-#endif
-    if (!go) { i = ray_uniform(N.skip); continue; }
-    const int leaf = ray_uniform(N.leaf);
-    if (leaf >= 0) {
-      const float4* q = tris + (size_t)4 * (size_t)(leaf >> 3);
-      const int cnt = leaf & 7;
-      for (int t = 0; t < cnt; t++) {
-        const float4 q1 = q[4*t + 1], q2 = q[4*t + 2];
-        const float x = ray_tri(p, v, vn, L, sp, q[4*t], q1, q2, q[4*t + 3]);
-        if (x >= 0.0f && x <= lim) {
-          cur = x; lim = x;
-          nrm[0] = q1.y * q2.z - q1.z * q2.y; nrm[1] = q1.z * q2.x - q1.x * q2.z; nrm[2] = q1.x * q2.y - q1.y * q2.x;
-        }
-      }
-    }
-    i = i + 1;
-  }
-  return cur;
-}
-
-// height field: ray_hfield (dev_ray.h) with the normal of the feature that gives the nearest hit — the base (0, 0, -1), a wall's outward
-// axis, or the geometric normal of the top triangle: over cell (r, c) triangle k is z = z00 + u A + w B with u = (X + sx) / dx - c and
-// w = (Y + sy) / dy - r, so its upward normal is (-A / dx, -B / dy, 1).  The candidates come in ray_hfield's order and replace the best
-// under ray_pick's rule (a strictly smaller x): the feature is the one whose x ray_hfield returned.
-RDEV float normal_hfield(const float* p, const float* v, const RayHField& H, const float* __restrict__ hd, float* nrm) {
-  nrm[0] = nrm[1] = nrm[2] = 0.0f;
-  const float sx = H.size[0], sy = H.size[1], sz = H.size[2], sb = H.size[3];
-  const float bmin[3] = {-sx, -sy, -sb}, bmax[3] = {sx, sy, sz};
-  float t0, t1;
-  if (!ray_slabs(p, v, bmin, bmax, t0, t1) || t1 < 0.0f) return -1.0f;
-  t0 = fmaxf(t0, 0.0f);
-  float best = -1.0f;
-  if (v[2] != 0.0f) {
-    const float x = (-sb - p[2]) / v[2];
-    if (fabsf(p[0] + x * v[0]) <= sx && fabsf(p[1] + x * v[1]) <= sy) {
-      const float nb = ray_pick(best, x);
-      if (nb != best) { best = nb; nrm[0] = 0.0f; nrm[1] = 0.0f; nrm[2] = -1.0f; }
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    const int ax = k >> 1;
-    const float w = (k & 1) ? 1.0f : -1.0f;
-    const float va = ax ? v[1] : v[0], pa = ax ? p[1] : p[0], sa = ax ? sy : sx, so = ax ? sx : sy;
-    if (va != 0.0f) {
-      const float x = (w * sa - pa) / va;
-      const float o = ax ? p[0] + x * v[0] : p[1] + x * v[1], z = p[2] + x * v[2];
-      if (x >= 0.0f && fabsf(o) <= so && z >= -sb) {
-        const float h = ax ? ray_hfield_height(H, hd, o, w * sa) : ray_hfield_height(H, hd, w * sa, o);
-        if (z <= h) {
-          const float nb = ray_pick(best, x);
-          if (nb != best) { best = nb; nrm[0] = ax ? 0.0f : w; nrm[1] = ax ? w : 0.0f; nrm[2] = 0.0f; }
-        }
-      }
-    }
-  }
-  const int nc = H.ncol, nr = H.nrow;
-  const float dx = 2.0f * sx / (float)(nc - 1), dy = 2.0f * sy / (float)(nr - 1);
-  const float gu = (p[0] + sx) / dx, gw = (p[1] + sy) / dy, ud = v[0] / dx, wd = v[1] / dy;
-  const float tolu = 4.8e-7f * (fabsf(gu) + (float)nc), tolw = 4.8e-7f * (fabsf(gw) + (float)nr);
-  const float ua = gu + t0 * ud, ub = gu + t1 * ud;
-  const int c0 = (int)fminf(fmaxf(floorf(fminf(ua, ub) - tolu), 0.0f), (float)(nc - 2));
-  const int c1 = (int)fminf(fmaxf(floorf(fmaxf(ua, ub) + tolu), 0.0f), (float)(nc - 2));
-  const float rtol = v[0] != 0.0f ? tolw + tolu * fabsf(wd / ud) : tolw;
-  for (int c = c0; c <= c1; c++) {
-    float ta = t0, tb = t1;
-    if (v[0] != 0.0f) {
-      const float a = ((float)c - gu) / ud, b = ((float)(c + 1) - gu) / ud;
-      ta = fmaxf(ta, fminf(a, b)); tb = fminf(tb, fmaxf(a, b));
-    }
-    if (ta > tb) ta = tb = 0.5f * (ta + tb);
-    const float wa = gw + ta * wd, wb = gw + tb * wd;
-    const int r0 = (int)fminf(fmaxf(floorf(fminf(wa, wb) - rtol), 0.0f), (float)(nr - 2));
-    const int r1 = (int)fminf(fmaxf(floorf(fmaxf(wa, wb) + rtol), 0.0f), (float)(nr - 2));
-    for (int r = r0; r <= r1; r++) {
-      const float z00 = hd[r * nc + c] * sz, z01 = hd[r * nc + c + 1] * sz, z10 = hd[(r + 1) * nc + c] * sz, z11 = hd[(r + 1) * nc + c + 1] * sz;
-      const float u0 = gu - (float)c, w0 = gw - (float)r;
-#pragma unroll
-      for (int k = 0; k < 2; k++) {
-        const float A = k ? z11 - z10 : z01 - z00, B = k ? z10 - z00 : z11 - z01;
-        const float den = v[2] - ud * A - wd * B;
-        if (den == 0.0f) continue;
-        const float x = (z00 + u0 * A + w0 * B - p[2]) / den;
-        const float u = (gu + x * ud) - (float)c, w = (gw + x * wd) - (float)r;
-        const bool in = k ? (w >= u - (tolu + tolw) && u >= -tolu && w <= 1.0f + tolw) : (u >= w - (tolu + tolw) && w >= -tolw && u <= 1.0f + tolu);
-        if (in) {
-          const float nb = ray_pick(best, x);
-          if (nb != best) { best = nb; nrm[0] = -A / dx; nrm[1] = -B / dy; nrm[2] = 1.0f; }
-        }
-      }
-    }
-  }
-  return best;
-}
+// triangles (mesh surface 1) and the height field: the feature that gives the hit is only known to the scan that finds it, so the normal
+// comes from dev_ray.h's own ray_trimesh<true> / ray_hfield<true> — the one walk the depth kernel took, run again on this geom alone.
 
 // ---- the normal of geom g's surface where the world-frame ray (p, v) meets it at parameter x: the geom's type / table row gi
 // (RayScene::ginfo), world pose (pos, mat: row-major, world = mat local) and size s in the env.  nw: world frame, not normalised,
@@ -193,7 +77,7 @@ RDEV void render_normal(const RayScene& W, const RayTris& T, const int4 gi, cons
     case MJH_GEOM_PLANE: n[2] = 1.0f; break;
     case MJH_GEOM_HFIELD: {
       const RayHField H = W.hf[gi.w];
-      normal_hfield(lp, lv, H, W.hf_data + H.adr, n);
+      ray_hfield<true>(lp, lv, H, W.hf_data + H.adr, n);
     } break;
     case MJH_GEOM_SPHERE: n[0] = h[0]; n[1] = h[1]; n[2] = h[2]; break;
     case MJH_GEOM_CAPSULE: normal_capsule(h, s, n); break;
@@ -207,7 +91,7 @@ RDEV void render_normal(const RayScene& W, const RayTris& T, const int4 gi, cons
     case RAY_TYPE_TRIMESH:
       if (T.mesh) {
         const RayTriMesh Mt = T.mesh[gi.w];
-        normal_trimesh(lp, lv, Mt, T.nodes + Mt.node, T.tris + (size_t)4 * (size_t)Mt.tri, x + 1e-3f * fabsf(x) + 1e-30f, n);
+        ray_trimesh<true>(lp, lv, Mt, T.nodes + Mt.node, T.tris + (size_t)4 * (size_t)Mt.tri, x + 1e-3f * fabsf(x) + 1e-30f, n);
       }
       break;
     default: break;

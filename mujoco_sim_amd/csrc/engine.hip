@@ -18,6 +18,7 @@
 #include "dev_ray.h"
 #include "dev_depth.h"
 #include "dev_render.h"
+#include "ray_tables.h"
 
 void mjh_set_error(const std::string& s);  // model_builder.cpp
 hipError_t mjh_launch_window(hipStream_t st, int nvt, int grid, size_t lds, const DConst* dC, const DState& S, int env0, int n, int nl, int wxf, int n32, int n64);   // window.hip
@@ -1901,11 +1902,7 @@ static int ray_tables(mjh_engine* e) {
       const bool ok = adr >= 0 && num > 0 && (long long)adr + num <= m->nmeshplane;
       double r2 = 0;
       for (int k = 0; k < m->mesh_vertnum[i]; k++) { const double* x = m->mesh_vert + 3 * ((size_t)m->mesh_vertadr[i] + k); r2 = std::max(r2, x[0]*x[0] + x[1]*x[1] + x[2]*x[2]); }
-      mt[i].adr = (int)pl.size(); mt[i].num = 0; mt[i].rbound = (float)std::sqrt(r2); mt[i].pad = 0.0f;
-      if (!ok) continue;
-      for (int k = adr; k < adr + num; k++) pl.push_back(make_float4((float)m->mesh_plane[4*k], (float)m->mesh_plane[4*k+1], (float)m->mesh_plane[4*k+2], (float)m->mesh_plane[4*k+3]));
-      while (pl.size() % 4) pl.push_back(make_float4(0.0f, 0.0f, 0.0f, 1.0f));
-      mt[i].num = (int)pl.size() - mt[i].adr;
+      ray_append_planes(m->mesh_plane + 4 * (size_t)(ok ? adr : 0), ok ? num : 0, (float)std::sqrt(r2), pl, mt[i]);
     }
     if (pl.empty()) pl.push_back(make_float4(0.0f, 0.0f, 0.0f, 1.0f));
     bool any = false;
@@ -1940,12 +1937,9 @@ static int ray_tri_tables(mjh_engine* e) {
     for (int i = 0; i < m->nmesh; i++) {
       const int adr = m->mesh_triadr[i], num = m->mesh_trinum[i];
       if (!(adr >= 0 && num > 0 && (long long)adr + num <= m->nmeshtri)) continue;
-      RayBvh B;
-      if (!ray_bvh_build(m->mesh_tri + 9 * (size_t)adr, num, B)) { mjh_set_error("mjh_ray: the triangles of mesh " + std::to_string(i) + " give no valid BVH (non-finite coordinates?)"); return MJH_ERR_ARG; }
-      if (nodes.size() + B.nodes.size() > 0x7fffffffull || tris.size() / RAY_TRI_FLOATS + (size_t)num > 0x0fffffffull) { mjh_set_error("mjh_ray: too many mesh triangles"); return MJH_ERR_ARG; }
-      mt[i] = RayTriMesh{(int)nodes.size(), (int)B.nodes.size(), (int)(tris.size() / RAY_TRI_FLOATS), num, B.rbound, B.r1, 0.0f, 0.0f};
-      nodes.insert(nodes.end(), B.nodes.begin(), B.nodes.end());
-      tris.insert(tris.end(), B.tris.begin(), B.tris.end());
+      const int bad = ray_append_bvh(m->mesh_tri + 9 * (size_t)adr, num, nodes, tris, mt[i]);
+      if (bad == RAY_APPEND_NO_BVH) { mjh_set_error("mjh_ray: the triangles of mesh " + std::to_string(i) + " give no valid BVH (non-finite coordinates?)"); return MJH_ERR_ARG; }
+      if (bad) { mjh_set_error("mjh_ray: too many mesh triangles"); return MJH_ERR_ARG; }
     }
     std::vector<int4> gi = e->ray_gi_mesh_host;
     bool any = false;

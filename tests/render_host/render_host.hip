@@ -1,7 +1,7 @@
 // render_host.hip — the shade kernel's own code (csrc/dev_render.h: __host__ __device__) evaluated on the CPU, behind the depth kernel's
 // own cast (csrc/dev_ray.h: the verdict, the compacted records, the walk).  Built as a shared object by tests/test_render_host.py,
-// never run on a GPU: render_host_image() takes one env's scene as plain arrays, builds the tables the engine builds (hull planes
-// padded to a multiple of four, a BVH per mesh with triangles: csrc/ray_bvh.h) and renders world-frame float32 rays, one pixel per ray,
+// never run on a GPU: render_host_image() takes one env's scene as plain arrays, builds the tables with the functions the engine builds
+// them with (csrc/ray_tables.h: hull planes padded to a multiple of four, a BVH per mesh with triangles) and renders world-frame float32 rays, one pixel per ray,
 // as mjh_depth_kernel and mjh_shade_kernel do for a lane: depth and geom id first, then the ray parameter recovered from the depth,
 // the normal on the one geom the pixel names, orientation, and the colour.  The comparison with the fp64 reference is tests/render_check.py's.
 // With -DRENDER_HOST_MAIN and the host part under AddressSanitizer / UBSan it is a stand-alone program: random scenes of every type over
@@ -18,6 +18,7 @@
 
 #include "../../include/mjhip.h"
 #include "../../mujoco_sim_amd/csrc/dev_render.h"
+#include "../../mujoco_sim_amd/csrc/ray_tables.h"
 
 // gtype: the type a ray sees (MJH_GEOM_*; MJH_GEOM_MESH: the hull of mesh gdata; 8: the triangles of mesh gdata; -1: invisible), gdata:
 // hfield / mesh id.  hf_dim [nhf][2] (nrow, ncol), hf_size [nhf][4], hf_adr [nhf] into hf_data.  Per mesh: planes [plane_adr, + plane_num)
@@ -42,17 +43,8 @@ extern "C" int render_host_image(int ngeom, const float* gpos, const float* gmat
   std::vector<RayTriMesh> tmesh((size_t)(nmesh > 0 ? nmesh : 1), RayTriMesh{0, 0, 0, 0, 0.0f, 0.0f, 0.0f, 0.0f});
   std::vector<RayNode> nodes; std::vector<float> trec;
   for (int i = 0; i < nmesh; i++) {
-    mesh[i].adr = (int)pl.size(); mesh[i].rbound = mesh_rbound[i]; mesh[i].pad = 0.0f;
-    for (int k = plane_adr[i]; k < plane_adr[i] + plane_num[i]; k++) pl.push_back(make_float4(planes[4*k], planes[4*k+1], planes[4*k+2], planes[4*k+3]));
-    while (pl.size() % 4) pl.push_back(make_float4(0.0f, 0.0f, 0.0f, 1.0f));
-    mesh[i].num = (int)pl.size() - mesh[i].adr;
-    if (tri_num[i] > 0) {
-      RayBvh B;
-      if (!ray_bvh_build(tris + 9 * (size_t)tri_adr[i], tri_num[i], B)) return -1;
-      tmesh[i] = RayTriMesh{(int)nodes.size(), (int)B.nodes.size(), (int)(trec.size() / RAY_TRI_FLOATS), tri_num[i], B.rbound, B.r1, 0.0f, 0.0f};
-      nodes.insert(nodes.end(), B.nodes.begin(), B.nodes.end());
-      trec.insert(trec.end(), B.tris.begin(), B.tris.end());
-    }
+    ray_append_planes(planes + 4 * (size_t)plane_adr[i], plane_num[i], mesh_rbound[i], pl, mesh[i]);
+    if (tri_num[i] > 0 && ray_append_bvh(tris + 9 * (size_t)tri_adr[i], tri_num[i], nodes, trec, tmesh[i]) != 0) return -1;
   }
   if (pl.empty()) pl.push_back(make_float4(0.0f, 0.0f, 0.0f, 1.0f));
   if (nodes.empty()) nodes.push_back(RayNode{});
@@ -103,6 +95,32 @@ extern "C" int render_host_image(int ngeom, const float* gpos, const float* gmat
     const float ndv = render_finish(n, v, vv);
     for (int k = 0; k < 3; k++) normal[3*i + k] = n[k];
     rgba[i] = g >= 0 ? render_color(make_float4(color[4*g], color[4*g+1], color[4*g+2], color[4*g+3]), ambient, diffuse, ndv) : bg;
+  }
+  return 0;
+}
+
+// Both instances of a walk of dev_ray.h on the same geom-frame rays: x0 what the instance without NRM returns, x1 and nrm [nray][3] what
+// the one with NRM returns and leaves.  ntri > 0: ray_trimesh over the BVH of `tris` (9 doubles each) with bound[i] per ray; else
+// ray_hfield over the nrow x ncol elevations hf_data with hf_size.  Returns 0, or -1 where the BVH could not be built.
+extern "C" int render_host_walk_pair(int nrow, int ncol, const float* hf_size, const float* hf_data, int ntri, const double* tris,
+                                     int nray, const float* P, const float* V, const float* bound, float* x0, float* x1, float* nrm) {
+  if (ntri > 0) {
+    std::vector<RayNode> nodes; std::vector<float> trec;
+    RayTriMesh M;
+    if (ray_append_bvh(tris, ntri, nodes, trec, M) != 0) return -1;
+    const float4* q = (const float4*)trec.data();
+    for (int i = 0; i < nray; i++) {
+      x0[i] = ray_trimesh(P + 3 * i, V + 3 * i, M, nodes.data(), q, bound[i]);
+      x1[i] = ray_trimesh<true>(P + 3 * i, V + 3 * i, M, nodes.data(), q, bound[i], nrm + 3 * i);
+    }
+    return 0;
+  }
+  RayHField H;
+  H.nrow = nrow; H.ncol = ncol; H.adr = 0; H.pad = 0;
+  for (int k = 0; k < 4; k++) H.size[k] = hf_size[k];
+  for (int i = 0; i < nray; i++) {
+    x0[i] = ray_hfield(P + 3 * i, V + 3 * i, H, hf_data);
+    x1[i] = ray_hfield<true>(P + 3 * i, V + 3 * i, H, hf_data, nrm + 3 * i);
   }
   return 0;
 }

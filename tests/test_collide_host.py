@@ -20,12 +20,11 @@ Every family now passes from the first rung of the ladder, 1e-6 (`passes from` i
 most 1.6 % (plane_mesh)."""
 import ctypes as C
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostbuild
 import pairgeom as pg
 from pairmodels import CAP, mesh_cloud, needed_tol, summarize
 
@@ -37,17 +36,9 @@ LADDER = [1e-6 * 10 ** (k / 2) for k in range(12)]
 MAXCON = 4
 
 
-def _hipcc():
-    return shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
-
-
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
-    hipcc = _hipcc()
-    assert hipcc, "hipcc is what builds this project"
-    so = tmp_path_factory.mktemp("collide_host") / "libcollide_host.so"
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O2", "-shared", "-fPIC", SRC, "-o", str(so)])
-    lib = C.CDLL(str(so))
+    lib = C.CDLL(hostbuild.shared(SRC, tmp_path_factory.mktemp("collide_host")))
     fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int)
     lib.collide_host_batch.argtypes = [C.c_int, C.c_int, fp, fp, fp, C.c_int, fp, fp, fp, C.c_float, fp, ip]
     lib.collide_host_batch.restype = None
@@ -127,20 +118,4 @@ def test_a_margin_brings_in_separated_pairs(host):
 def test_sanitized_stand_alone_run_is_clean(tmp_path):
     """the same source with its own main under AddressSanitizer / UBSan (host part only): 2e5 calls over the ten routines, aligned
     orientations and coincident centres among them, into an exactly-sized staging array"""
-    hipcc = _hipcc()
-    assert hipcc
-    probe = tmp_path / "probe.hip"
-    probe.write_text("int main() { return 0; }\n")
-    san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined"]
-    pr = subprocess.run([hipcc, "--offload-arch=gfx950", *san, str(probe), "-o", str(tmp_path / "probe")], capture_output=True, text=True)
-    if pr.returncode != 0:
-        # only a missing sanitizer runtime excuses the run; any other failure of the probe is a failure
-        assert any(w in pr.stderr.lower() for w in ("asan", "ubsan", "sanitizer", "clang_rt")), pr.stderr[:2000]
-        pytest.skip("AddressSanitizer / UBSan runtime not available to hipcc")
-    exe = tmp_path / "collide_host_san"
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O1", "-g", "-DCOLLIDE_HOST_MAIN", *san, SRC, "-o", str(exe)])
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1"))
-    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[:4000]
-    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr[:2000])
-    assert r.stderr.strip() == "", r.stderr[:2000]
-    assert " 0 failures" in r.stdout
+    hostbuild.sanitized_run(SRC, "COLLIDE_HOST_MAIN", tmp_path)

@@ -7,11 +7,11 @@ Cull: on 20 000 random (tile, sphere) cases per image size, whenever a pixel-cen
 predicate keeps the sphere — zero exceptions; the share of spheres culled among those no ray hits is printed, not asserted."""
 import ctypes as C
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
+
+import hostbuild
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "depth_host", "depth_host.hip")
@@ -19,17 +19,9 @@ SIZES = [(1, 1), (8, 8), (30, 20), (64, 48)]      # (width, height)
 FOVY = [20.0, 60.0, 120.0]
 
 
-def _hipcc():
-    return shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
-
-
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
-    hipcc = _hipcc()
-    assert hipcc, "hipcc is what builds this project"
-    so = tmp_path_factory.mktemp("depth_host") / "libdepth_host.so"
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O2", "-shared", "-fPIC", SRC, "-o", str(so)])
-    lib = C.CDLL(str(so))
+    lib = C.CDLL(hostbuild.shared(SRC, tmp_path_factory.mktemp("depth_host")))
     fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int)
     lib.depth_host_dirs.argtypes = [C.c_int, C.c_int, C.c_float, fp]
     lib.depth_host_dirs.restype = None

@@ -17,12 +17,11 @@ The frame composition (RAY_FRAME, through
 ray_host_frame) is compared with numpy fp64.  The comparison of the casts is tests/ray_check.py's, the one of tests/test_gpu_depth.py."""
 import ctypes as C
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostbuild
 import ray_mesh_ref as rm
 import ray_ref as rr
 from ray_check import check
@@ -34,18 +33,10 @@ PRIMS = [(rr.PLANE, (3.0, 2.0, 0.05))] + rr.PRIMITIVES
 NAMES = {rr.PLANE: "plane", rr.SPHERE: "sphere", rr.CAPSULE: "capsule", rr.ELLIPSOID: "ellipsoid", rr.CYLINDER: "cylinder", rr.BOX: "box"}
 
 
-def _hipcc():
-    return shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
-
-
 @pytest.fixture(scope="module")
 def host_lib(tmp_path_factory):
     """tests/ray_host/ray_host.hip as a shared object"""
-    hipcc = _hipcc()
-    assert hipcc, "hipcc is what builds this project"
-    so = tmp_path_factory.mktemp("ray_host") / "libray_host.so"
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O2", "-shared", "-fPIC", SRC, "-o", str(so)])
-    return C.CDLL(str(so))
+    return C.CDLL(hostbuild.shared(SRC, tmp_path_factory.mktemp("ray_host")))
 
 
 @pytest.fixture(scope="module")
@@ -122,20 +113,7 @@ def test_sanitized_stand_alone_run_is_clean(tmp_path):
     """the same source with its own main under AddressSanitizer / UBSan (host part only): 2e5 rays per terrain over an exactly-sized
     elevation array, border lines and corner nodes included, the primitive families, and the scene cast (1, 63, 64, 65 and 130
     geoms of every type over exactly-sized pose, size, ginfo, table and record arrays; every visibility rule; both staging orders)"""
-    hipcc = _hipcc()
-    assert hipcc
-    probe = tmp_path / "probe.hip"
-    probe.write_text("int main() { return 0; }\n")
-    san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined"]
-    if subprocess.run([hipcc, "--offload-arch=gfx950", *san, str(probe), "-o", str(tmp_path / "probe")], capture_output=True).returncode != 0:
-        pytest.skip("AddressSanitizer / UBSan runtime not available to hipcc")
-    exe = tmp_path / "ray_host_san"
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O1", "-g", "-DRAY_HOST_MAIN", *san, SRC, "-o", str(exe)])
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1"))
-    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[:4000]
-    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr[:2000])
-    assert r.stderr.strip() == "", r.stderr[:2000]
-    assert " 0 failures" in r.stdout
+    hostbuild.sanitized_run(SRC, "RAY_HOST_MAIN", tmp_path)
 
 
 # ------------------------------------------------------------------ whole scenes through the kernels' shared code

@@ -13,12 +13,11 @@ Measured: 0 wrong rays in every family, worst scaled error 6.0e-7 (ellipsoid poi
 (PR2's largest mesh, in face plane: the one ray in 25 that lies in the facet's plane exactly, plus a few that graze an edge)."""
 import ctypes as C
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostbuild
 import ray_mesh_ref as rm
 import ray_ref as rr
 
@@ -28,17 +27,9 @@ TOL = 5e-5
 NRAY = 400
 
 
-def _hipcc():
-    return shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
-
-
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
-    hipcc = _hipcc()
-    assert hipcc, "hipcc is what builds this project"
-    so = tmp_path_factory.mktemp("ray_mesh_host") / "libray_mesh_host.so"
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O2", "-shared", "-fPIC", SRC, "-o", str(so)])
-    lib = C.CDLL(str(so))
+    lib = C.CDLL(hostbuild.shared(SRC, tmp_path_factory.mktemp("ray_mesh_host")))
     fp = C.POINTER(C.c_float)
     lib.ray_mesh_host_cast.argtypes = [fp, C.c_int, C.c_int, fp, fp, fp]
     lib.ray_mesh_host_cast.restype = None
@@ -111,17 +102,4 @@ def test_sanitized_stand_alone_run_is_clean(tmp_path):
     """the same source with its own main under AddressSanitizer / UBSan (host part only): plane sets of every length 1 .. 13 and of 55,
     150 and 666 planes in exactly-sized heap arrays, rays from 3 m and 30 m, from inside, with zero components, along the axes and
     in the plane of a face"""
-    hipcc = _hipcc()
-    assert hipcc
-    probe = tmp_path / "probe.hip"
-    probe.write_text("int main() { return 0; }\n")
-    san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined"]
-    if subprocess.run([hipcc, "--offload-arch=gfx950", *san, str(probe), "-o", str(tmp_path / "probe")], capture_output=True).returncode != 0:
-        pytest.skip("AddressSanitizer / UBSan runtime not available to hipcc")
-    exe = tmp_path / "ray_mesh_host_san"
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O1", "-g", "-DRAY_MESH_HOST_MAIN", *san, SRC, "-o", str(exe)])
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1"))
-    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[:4000]
-    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr[:2000])
-    assert r.stderr.strip() == "", r.stderr[:2000]
-    assert " 0 failures" in r.stdout
+    hostbuild.sanitized_run(SRC, "RAY_MESH_HOST_MAIN", tmp_path)

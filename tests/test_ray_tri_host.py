@@ -15,12 +15,11 @@ that lies in the facet's plane exactly, plus the open surface's rim); the rays a
 those at the flat quad's edges (its in-plane family misses throughout, as the reference does)."""
 import ctypes as C
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostbuild
 import ray_mesh_ref as rm
 import ray_tri_ref as rt
 
@@ -29,10 +28,6 @@ SRC = os.path.join(ROOT, "tests", "ray_host", "ray_tri_host.hip")
 TOL = 5e-5
 NRAY = 400
 NAMES = ["torus", "jaw", "sheet", "flat_quad", "box12", "five"]
-
-
-def _hipcc():
-    return shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
 
 
 class Host:
@@ -67,11 +62,7 @@ class Host:
 
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
-    hipcc = _hipcc()
-    assert hipcc, "hipcc is what builds this project"
-    so = tmp_path_factory.mktemp("ray_tri_host") / "libray_tri_host.so"
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O2", "-shared", "-fPIC", SRC, "-o", str(so)])
-    return Host(str(so))
+    return Host(hostbuild.shared(SRC, tmp_path_factory.mktemp("ray_tri_host")))
 
 
 @pytest.fixture(scope="module")
@@ -202,17 +193,4 @@ def test_sanitized_stand_alone_run_is_clean(tmp_path):
     """the same source with its own main under AddressSanitizer / UBSan (host part only): BVHs of 1 .. 40 random triangles, of a
     576- and a 4800-triangle torus and of one triangle without area, the tables in exactly-sized heap arrays; every ray through the BVH
     and through the loop, fresh and seeded"""
-    hipcc = _hipcc()
-    assert hipcc
-    probe = tmp_path / "probe.hip"
-    probe.write_text("int main() { return 0; }\n")
-    san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined"]
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", *san, str(probe), "-o", str(tmp_path / "probe")], capture_output=True, text=True)
-    assert r.returncode == 0, "hipcc cannot build a host program with AddressSanitizer / UBSan: " + r.stderr[-2000:]
-    exe = tmp_path / "ray_tri_host_san"
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O1", "-g", "-DRAY_TRI_HOST_MAIN", *san, SRC, "-o", str(exe)])
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1"))
-    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[:4000]
-    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr[:2000])
-    assert r.stderr.strip() == "", r.stderr[:2000]
-    assert " 0 failures" in r.stdout
+    hostbuild.sanitized_run(SRC, "RAY_TRI_HOST_MAIN", tmp_path)

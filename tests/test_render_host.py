@@ -13,12 +13,11 @@ normal error 5.1e-6; the height field's directed and random rays (374) 0.0053, 1
 0.0018, 1.2e-7; the flat panel's four rays 0."""
 import ctypes as C
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostbuild
 import ray_mesh_ref as rm
 import ray_ref as rr
 import render_check as rc
@@ -27,10 +26,6 @@ import render_ref as rf
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "render_host", "render_host.hip")
 TRIMESH = 8      # csrc/dev_ray.h: RAY_TYPE_TRIMESH
-
-
-def _hipcc():
-    return shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
 
 
 def f32_scene(scene):
@@ -43,6 +38,22 @@ class Host:
         self.lib.render_host_image.argtypes = [C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 8 + \
             [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float] + [C.c_void_p] * 5
         self.lib.render_host_image.restype = C.c_int
+        self.lib.render_host_walk_pair.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6
+        self.lib.render_host_walk_pair.restype = C.c_int
+
+    def walk_pair(self, P, V, hfield=None, tris=None, bound=None):
+        """(x of the instance without NRM, x of the one with it, the normal that one leaves [n, 3]) of geom-frame float32 rays through
+        ray_hfield (hfield: elevations [nrow, ncol] and size[4]) or ray_trimesh (tris [nt, 3, 3]; bound per ray, default 3e38)"""
+        a = lambda x, t=np.float32: np.ascontiguousarray(x, dtype=t)
+        P, V = a(P), a(V)
+        n = len(P)
+        el, size = (a(hfield[0]), a(hfield[1])) if hfield is not None else (a(np.zeros((2, 2))), a(np.zeros(4)))
+        t = a(tris if tris is not None else np.zeros((0, 3, 3)), np.float64)
+        bd = a(np.full(n, 3e38) if bound is None else bound)
+        x0 = np.full(n, 7.0, np.float32); x1 = np.full(n, 7.0, np.float32); nrm = np.full((n, 3), 7.0, np.float32)
+        p = lambda x: x.ctypes.data
+        assert self.lib.render_host_walk_pair(el.shape[0], el.shape[1], p(size), p(el), len(t), p(t), n, p(P), p(V), p(bd), p(x0), p(x1), p(nrm)) == 0
+        return x0, x1, nrm
 
     def render(self, m, scene, rays, surface=None, range_=0, ambient=0.3, diffuse=0.7, background=(0.0, 0.0, 0.0, 0.0)):
         """(depth, gid, normal [n, 3], rgba uint8 [n, 4]) of float32 world-frame rays through model m posed as `scene` (float32 numbers);
@@ -86,11 +97,7 @@ class Host:
 
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
-    hipcc = _hipcc()
-    assert hipcc, "hipcc is what builds this project"
-    so = tmp_path_factory.mktemp("render_host") / "librender_host.so"
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O2", "-shared", "-fPIC", SRC, "-o", str(so)])
-    return Host(str(so))
+    return Host(hostbuild.shared(SRC, tmp_path_factory.mktemp("render_host")))
 
 
 @pytest.fixture(scope="module")
@@ -214,21 +221,100 @@ def test_flat_shade_is_exact_and_the_background_is_kept(host, models):
     rc.check_render("host primitives front, range 1", d1, g1, n1, c1, scene, rays, rc.model_colours(m), scale=np.linalg.norm(rays[1], axis=1))
 
 
+# ------------------------------------------------------------------ one walk, two instances (csrc/dev_ray.h: ray_hfield<NRM>, ray_trimesh<NRM>)
+def _pair_rays(rng, lo, hi, inside, n):
+    """n geom-frame rays from around the box [lo, hi] aimed into it, n from the points `inside` (a random direction each)"""
+    lo, hi = np.asarray(lo, float), np.asarray(hi, float)
+    c, r = 0.5 * (lo + hi), np.linalg.norm(hi - lo)
+    u = rng.normal(size=(n, 3)); u /= np.linalg.norm(u, axis=1, keepdims=True)
+    P = c + u * rng.uniform(0.8, 3.0, size=(n, 1)) * r
+    V = (rng.uniform(lo - 0.1 * r, hi + 0.1 * r, size=(n, 3)) - P) * rng.uniform(0.3, 2.0, size=(n, 1))
+    Pi = np.asarray(inside, float)[rng.integers(0, len(inside), n)]
+    Vi = rng.normal(size=(n, 3))
+    return np.vstack([P, Pi]), np.vstack([V, Vi])
+
+
+def _same_walk(x0, x1, nrm, what):
+    assert x0.tobytes() == x1.tobytes(), f"{what}: the instance with NRM returns other bits"
+    assert np.array_equal(np.abs(nrm).max(axis=1) > 0, x1 >= 0), f"{what}: a non-zero normal exactly where there is a hit"
+    assert (x1 >= 0).sum() > len(x1) // 4 and (x1 < 0).sum() > 20, f"{what}: hits and misses both occur"
+
+
+@pytest.mark.parametrize("nrow,ncol", [(2, 2), (3, 4)])
+def test_hfield_walk_with_normal_is_the_walk_without(host, nrow, ncol):
+    """2 x 2: one cell — both triangles, four walls, the base; 3 x 4: strips and rows to walk.  Rays from outside, from inside the solid,
+    and on and along grid lines (column lines, row lines, the cells' diagonals)"""
+    rng = np.random.default_rng(100 * nrow + ncol)
+    size = np.array([0.6, 0.4, 0.3, 0.1], np.float32)
+    el = rng.uniform(0.2, 1.0, size=(nrow, ncol)).astype(np.float32)
+    sx, sy, sz, sb = size.astype(float)
+    inside = rng.uniform([-sx, -sy, -sb], [sx, sy, 0.2 * sz], size=(50, 3))      # below the lowest elevation: in the solid
+    P, V = _pair_rays(rng, [-sx, -sy, -sb], [sx, sy, sz], inside, 600)
+    # grid lines: origins on a line x = column / y = row (exact in the grid's own units for these sizes or not: both kinds occur), the
+    # direction within the line's vertical plane; the diagonal of a cell, seen from above and from below
+    xs, ys = np.linspace(-sx, sx, ncol), np.linspace(-sy, sy, nrow)
+    Pl, Vl = [], []
+    for k in range(300):
+        up = 1.0 if k % 2 else -1.0
+        x, y = xs[rng.integers(ncol)], ys[rng.integers(nrow)]
+        t = rng.uniform(-1.2, 1.2)
+        Pl += [[x, t * sy, -up * 1.0], [t * sx, y, -up * 1.0], [x, y, -up * 1.0]]
+        Vl += [[0.0, rng.uniform(-0.5, 0.5), up], [rng.uniform(-0.5, 0.5), 0.0, up], [0.0, 0.0, up]]
+        a, b = rng.uniform(-1.0, 2.0, 2)      # two points of the diagonal u = w of cell (0, 0), continued beyond it
+        dx, dy = 2 * sx / (ncol - 1), 2 * sy / (nrow - 1)
+        Pl.append([-sx + a * dx, -sy + a * dy, -up * 1.0]); Vl.append([(b - a) * dx, (b - a) * dy, up * 2.0])
+    rays = rr.f32(np.vstack([P, Pl]), np.vstack([V, Vl]))
+    x0, x1, nrm = host.walk_pair(rays[0], rays[1], hfield=(el, size))
+    _same_walk(x0, x1, nrm, f"height field {nrow} x {ncol}")
+    hit = nrm[x1 >= 0]
+    axes = {tuple(r) for r in hit[hit[:, 2] != 1.0].astype(int)}
+    assert axes == {(0, 0, -1), (1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0)}, "the base and the four walls give hits"
+    tops = {tuple(r) for r in hit[hit[:, 2] == 1.0]}
+    assert len(tops) == 2 * (nrow - 1) * (ncol - 1), "and so does every top triangle"
+
+
+def _tetra():
+    c = np.array([[1, 1, 1], [1, -1, -1], [-1, 1, -1], [-1, -1, 1]], float) * 0.3
+    return np.array([[c[j] for j in range(4) if j != k] for k in range(4)])
+
+
+def _box12():
+    h = np.array([0.5, 0.3, 0.2])
+    c = np.array([[x, y, z] for x in (-1, 1) for y in (-1, 1) for z in (-1, 1)], float) * h
+    quads = [(0, 1, 3, 2), (4, 6, 7, 5), (0, 4, 5, 1), (2, 3, 7, 6), (0, 2, 6, 4), (1, 5, 7, 3)]
+    return np.array([[c[q[0]], c[q[i]], c[q[i + 1]]] for q in quads for i in (1, 2)])
+
+
+@pytest.mark.parametrize("name", ["tetrahedron", "box12"])
+def test_trimesh_walk_with_normal_is_the_walk_without(host, name):
+    """a tetrahedron: one leaf; a box of 12 triangles: four leaves under inner nodes with a skip.  Rays from outside, from inside the
+    solid, and at the corners and edge midpoints; unbounded, then with the bound a little above the hit (render_normal's)"""
+    rng = np.random.default_rng(len(name))
+    tris = _tetra() if name == "tetrahedron" else _box12()
+    corners = tris.reshape(-1, 3)
+    lo, hi = corners.min(axis=0), corners.max(axis=0)
+    P, V = _pair_rays(rng, lo, hi, rng.uniform(-0.02, 0.02, size=(50, 3)), 800)
+    aim = np.vstack([corners, 0.5 * (tris + np.roll(tris, 1, axis=1)).reshape(-1, 3)])      # shared vertices and edges
+    Pa = rng.normal(size=(len(aim), 3)) * 1.5
+    rays = rr.f32(np.vstack([P, Pa]), np.vstack([V, aim - Pa]))
+    x0, x1, nrm = host.walk_pair(rays[0], rays[1], tris=tris)
+    _same_walk(x0, x1, nrm, name)
+    assert (x1[800:1600] >= 0).all(), "from inside a closed mesh every ray hits"
+    bound = np.where(x1 >= 0, x1 + np.float32(1e-3) * np.abs(x1) + np.float32(1e-30), np.float32(3e38)).astype(np.float32)
+    b0, b1, bn = host.walk_pair(rays[0], rays[1], tris=tris, bound=bound)
+    _same_walk(b0, b1, bn, name + ", bounded")
+    assert b1.tobytes() == x1.tobytes() and bn.tobytes() == nrm.tobytes(), "the bound above the hit prunes nothing the scan would take"
+    # e1 x e2 of one of the mesh's triangles, and of one the hit point lies in the plane of
+    N = np.cross(tris[:, 1] - tris[:, 0], tris[:, 2] - tris[:, 0])
+    h = x1 >= 0
+    X = rays[0][h] + x1[h, None].astype(float) * rays[1][h]
+    for n, x in zip(nrm[h].astype(float), X):
+        k = np.argmin(np.abs(N - n).max(axis=1))
+        assert np.abs(N[k] - n).max() < 1e-6 and abs(N[k] @ (x - tris[k, 0])) < 1e-5 * np.linalg.norm(N[k])
+
+
 def test_sanitized_stand_alone_run_is_clean(tmp_path):
     """the same source with its own main under AddressSanitizer / UBSan (host part only): random scenes of 1 .. 130 geoms of every type,
     hulls and triangle meshes included, over exactly-sized arrays; rays from outside and from inside the geoms; every hit a unit normal
     that faces its ray, every miss the zero normal and the background"""
-    hipcc = _hipcc()
-    assert hipcc
-    probe = tmp_path / "probe.hip"
-    probe.write_text("int main() { return 0; }\n")
-    san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined"]
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", *san, str(probe), "-o", str(tmp_path / "probe")], capture_output=True, text=True)
-    assert r.returncode == 0, "hipcc cannot link the AddressSanitizer / UBSan runtime: the check cannot run\n" + r.stderr[:2000]
-    exe = tmp_path / "render_host_san"
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O1", "-g", "-DRENDER_HOST_MAIN", *san, SRC, "-o", str(exe)])
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1"))
-    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[:4000]
-    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr[:2000])
-    assert r.stderr.strip() == "", r.stderr[:2000]
-    assert " 0 failures" in r.stdout
+    hostbuild.sanitized_run(SRC, "RENDER_HOST_MAIN", tmp_path)

@@ -1,9 +1,11 @@
-"""Every dist / geomid / depth array of a fixed set of small scenes in one .npz: the bit-for-bit A/B of two builds of the library
+"""Every dist / geomid / depth / normal / rgba array of a fixed set of small scenes in one .npz: the bit-for-bit A/B of two builds of the library
 (MJHIP_LIB selects the build).  The scenes are the smallest that reach each path the ray and depth kernels share, at 4 envs, made
 with the builders of the GPU tests: the primitives with a camera and a site on a free body (world-frame rays of 1, 63, 65 and 130;
 site-frame rays; per-env rays; bodyexclude, flg_static = 0, a cutoff; per-env geom sizes; an inactive slot), the height field, the
 mesh model in mesh modes 0 and 1, the tetrahedron field in mesh mode 1, more than 64 spheres; images of 1x1, 9x8 and 30x20 with the
-cull on and off and range on and off.
+cull on and off and range on and off.  Mesh surface 1 (the meshes' own triangles) for the mesh model and the tetrahedron field, through
+both calls.  For every camera and size mjh_render's normal and rgba images with range on and off, and the models of the render tests
+(tests/render_check.py): the height field from the side and from below (its base and walls), the meshes as hulls and as triangles.
 
     python tools/ray_depth_dump.py OUT.npz
     python tools/ray_depth_dump.py --compare A.npz B.npz      (exit status 1 and the first array that differs, if any)
@@ -42,6 +44,7 @@ def dump(path):
     import mujoco_sim_amd as ms
     import ray_mesh_ref as rm
     import ray_ref as rr
+    import render_check as rc
     import test_gpu_depth as td
     from depth_bench import TETRA_VIEW, tetra_with_camera, world_rays
     from helpers import D, set_opt
@@ -60,6 +63,10 @@ def dump(path):
                 for rng in (0, 1):
                     d, g = e.depth(cam, w, h, cull=cull, range=rng, **kw)
                     out[f"{tag}/{w}x{h}/cull{cull}/range{rng}/depth"], out[f"{tag}/{w}x{h}/cull{cull}/range{rng}/geomid"] = d, g
+            for rng in (0, 1):
+                d, g, nrm, col = e.render(cam, w, h, range=rng, **kw)
+                for k, a in (("depth", d), ("geomid", g), ("normal", nrm), ("rgba", col)):
+                    out[f"{tag}/{w}x{h}/render/range{rng}/{k}"] = a
 
     def prim_model():
         """the primitives with the two static views, and a free ball that carries a camera and a site"""
@@ -150,11 +157,32 @@ def dump(path):
         e.ray_mesh_mode = mode
         rays(f"mesh/mode{mode}/world", e, Pm, Vm)
         images(f"mesh/mode{mode}/cam", e, "cam", sizes=[(9, 8), (30, 20)])
+    e.ray_mesh_surface = 1
+    rays("mesh/surface1/world", e, Pm, Vm)
+    images("mesh/surface1/cam", e, "cam", sizes=[(9, 8), (30, 20)])
     e.close()
     e = ms.Engine(tetra_with_camera(lib), NENV)
     e.ray_mesh_mode = 1
-    rays("tetra/world", e, *world_rays(TETRA_VIEW, 13, 10))
-    images("tetra/cam", e, 0)
+    for surface in (0, 1):
+        e.ray_mesh_surface = surface
+        tag = "tetra" if surface == 0 else "tetra/surface1"
+        rays(tag + "/world", e, *world_rays(TETRA_VIEW, 13, 10))
+        images(tag + "/cam", e, 0)
+    e.close()
+
+    # ---- the render tests' models: the height field's top, walls and base, the non-convex meshes as hulls and as triangles
+    e = ms.Engine(rc.hfield_model(lib), NENV)
+    images("render_hfield/cam", e, "cam", sizes=[(9, 8), (30, 20)])
+    images("render_hfield/under", e, "under", sizes=[(9, 8), (30, 20)])
+    e.close()
+    mm, _ = rc.meshes_model(lib)
+    e = ms.Engine(mm, NENV)
+    e.ray_mesh_mode = 1
+    Pr, Vr = world_rays(rc.VIEW_MESHES, 13, 10)
+    for surface in (0, 1):
+        e.ray_mesh_surface = surface
+        rays(f"render_meshes/surface{surface}/world", e, Pr, Vr)
+        images(f"render_meshes/surface{surface}/cam", e, "cam", sizes=[(9, 8), (24, 16)])
     e.close()
 
     # ---- more geoms than one staging pass holds
