@@ -45,6 +45,7 @@ DEV void wn_fold_8to4(const float* y, float* z) {   // lanes with bit 2 clear ke
 DEV float wn_fold16(const float* x) {
   float y[8], z[4];
   // lanes 0..7 keep values 0..7, lanes 8..15 values 8..15 (partner: 8 lanes away)
+  // (the 32-slot instance's reduce, as it was: two wait states in front — its products are not pinned)
   asm volatile("s_nop 1\n\t"
                WN_ROR2("%0", "%8", "%16", 8, 0x3, 8, 0xc) WN_ROR2("%1", "%9", "%17", 8, 0x3, 8, 0xc) WN_ROR2("%2", "%10", "%18", 8, 0x3, 8, 0xc) WN_ROR2("%3", "%11", "%19", 8, 0x3, 8, 0xc)
                WN_ROR2("%4", "%12", "%20", 8, 0x3, 8, 0xc) WN_ROR2("%5", "%13", "%21", 8, 0x3, 8, 0xc) WN_ROR2("%6", "%14", "%22", 8, 0x3, 8, 0xc) WN_ROR2("%7", "%15", "%23", 8, 0x3, 8, 0xc)
@@ -54,18 +55,61 @@ DEV float wn_fold16(const float* x) {
   wn_fold_8to4(y, z);
   return wn_fold_tail(z);
 }
-// 8 values: lanes 2j and 2j + 1 both receive the sum of x[j]   (16 instructions: every stage halves the values a lane keeps)
-DEV float wn_fold8(const float* x) {
-  float y[4], z[2];
-  asm volatile("s_nop 1\n\t" WN_ROR2("%0", "%4", "%8", 8, 0x3, 8, 0xc) WN_ROR2("%1", "%5", "%9", 8, 0x3, 8, 0xc) WN_ROR2("%2", "%6", "%10", 8, 0x3, 8, 0xc) WN_ROR2("%3", "%7", "%11", 8, 0x3, 8, 0xc)
-               : "=&v"(y[0]), "=&v"(y[1]), "=&v"(y[2]), "=&v"(y[3]) : "v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3]), "v"(x[4]), "v"(x[5]), "v"(x[6]), "v"(x[7]));   // lanes 0..7: values 0..3, lanes 8..15: values 4..7
-  asm volatile(WN_ROR2("%0", "%2", "%4", 12, 0x5, 4, 0xa) WN_ROR2("%1", "%3", "%5", 12, 0x5, 4, 0xa)
-               : "=&v"(z[0]), "=&v"(z[1]) : "v"(y[0]), "v"(y[1]), "v"(y[2]), "v"(y[3]));                                  // lane bit 2 clear: values 0, 1 of the half; set: 2, 3
-  const bool b1 = (threadIdx.x & 2) != 0;
-  const float s = b1 ? z[1] : z[0], o = b1 ? z[0] : z[1];
-  float r = s + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, o), 0x4E, 0xf, 0xf, true));   // value index = 4 bit3 + 2 bit2 + bit1 of the lane = lane >> 1
-  MJH_DPP_ADD(r, 0xB1, 0xf, true);                                                                                             // + the neighbour lane (bit 0): both keep the value
-  return r;
+// Both transpose-reduces of the 24-slot forms — 16 values (wn_fold16's) and 8 values (lanes 2j and 2j + 1 both receive the sum of x[16 + j]: every stage
+// halves the values a lane keeps) — as two statements: the stages of the sixteen values first, then the stages of the eight with BOTH tails.  A tail's
+// selects (lane bit 1, then bit 0, as wave masks in scalar registers) each write a register that a DPP add reads next; the selects and adds of one
+// reduce stand in the two wait states of the other's, so no state is idle (left to the compiler, the two tails carried four `s_nop 1` and four
+// `s_nop 0`).  Stages write in place (a DPP add reads its sources before it writes).
+// No wait state in front, by construction: the first statement's first reads are x[0] and x[8], and the callers form those two products first and
+// every other product behind them (wn_products24: the others depend on an empty statement that takes the two) — ten instructions between; x[16 .. 23]
+// are complete in front of the first statement (a second empty statement takes them) and are read behind its 24 instructions.
+// ACC: r16 is the accumulator a_lo, and `a_lo += sum` stands inside, in front of the eight values' last add: with the caller's `a_hi += r8` that is
+// two instructions between the write of a_lo and the next dot's first DPP read of it (wn_dot<NV, false>), whatever the compiler does around them.
+// Every value is formed by the instructions of wn_fold16 and of the eight-value reduce on the same operands: bitwise.
+#define WN_FOLD24_BODY \
+    WN_ROR2("%[ya0]", "%[x16]", "%[x20]", 8, 0x3, 8, 0xc) WN_ROR2("%[ya1]", "%[x17]", "%[x21]", 8, 0x3, 8, 0xc) WN_ROR2("%[ya2]", "%[x18]", "%[x22]", 8, 0x3, 8, 0xc) WN_ROR2("%[ya3]", "%[x19]", "%[x23]", 8, 0x3, 8, 0xc) \
+    WN_ROR2("%[ya0]", "%[ya0]", "%[ya2]", 12, 0x5, 4, 0xa) WN_ROR2("%[ya1]", "%[ya1]", "%[ya3]", 12, 0x5, 4, 0xa) \
+    "v_cndmask_b32_e64 %[t0], %[z2], %[z0], %[m1]\n\t" "v_cndmask_b32_e64 %[t1], %[z3], %[z1], %[m1]\n\t" "v_cndmask_b32_e64 %[t2], %[z0], %[z2], %[m1]\n\t" \
+    "v_cndmask_b32_e64 %[t3], %[z1], %[z3], %[m1]\n\t" "v_cndmask_b32_e64 %[ya2], %[ya1], %[ya0], %[m1]\n\t" "v_cndmask_b32_e64 %[ya3], %[ya0], %[ya1], %[m1]\n\t"
+template <bool ACC> DEV void wn_fold24(const float* x, float& r16, float& r8) {
+  float y[8], ya[4], t[4];
+  const unsigned long long m1 = 0xccccccccccccccccull, m0 = 0xaaaaaaaaaaaaaaaaull;      // lanes with bit 1 / bit 0 of the lane index set
+  // sixteen values: lanes 0..7 keep values 0..7, lanes 8..15 values 8..15; then lanes with bit 2 clear values 0..3 of the half, the others 4..7 (in y[0..3])
+  asm volatile(WN_ROR2("%[y0]", "%[x0]", "%[x8]", 8, 0x3, 8, 0xc) WN_ROR2("%[y1]", "%[x1]", "%[x9]", 8, 0x3, 8, 0xc) WN_ROR2("%[y2]", "%[x2]", "%[x10]", 8, 0x3, 8, 0xc) WN_ROR2("%[y3]", "%[x3]", "%[x11]", 8, 0x3, 8, 0xc)
+               WN_ROR2("%[y4]", "%[x4]", "%[x12]", 8, 0x3, 8, 0xc) WN_ROR2("%[y5]", "%[x5]", "%[x13]", 8, 0x3, 8, 0xc) WN_ROR2("%[y6]", "%[x6]", "%[x14]", 8, 0x3, 8, 0xc) WN_ROR2("%[y7]", "%[x7]", "%[x15]", 8, 0x3, 8, 0xc)
+               WN_ROR2("%[y0]", "%[y0]", "%[y4]", 12, 0x5, 4, 0xa) WN_ROR2("%[y1]", "%[y1]", "%[y5]", 12, 0x5, 4, 0xa) WN_ROR2("%[y2]", "%[y2]", "%[y6]", 12, 0x5, 4, 0xa) WN_ROR2("%[y3]", "%[y3]", "%[y7]", 12, 0x5, 4, 0xa)
+               : [y0] "=&v"(y[0]), [y1] "=&v"(y[1]), [y2] "=&v"(y[2]), [y3] "=&v"(y[3]), [y4] "=&v"(y[4]), [y5] "=&v"(y[5]), [y6] "=&v"(y[6]), [y7] "=&v"(y[7])
+               : [x0] "v"(x[0]), [x1] "v"(x[1]), [x2] "v"(x[2]), [x3] "v"(x[3]), [x4] "v"(x[4]), [x5] "v"(x[5]), [x6] "v"(x[6]), [x7] "v"(x[7]), [x8] "v"(x[8]), [x9] "v"(x[9]), [x10] "v"(x[10]), [x11] "v"(x[11]), [x12] "v"(x[12]), [x13] "v"(x[13]), [x14] "v"(x[14]), [x15] "v"(x[15]));
+  // eight values: lanes 0..7: values 0..3, lanes 8..15: values 4..7; then lane bit 2 clear: values 0, 1 of the half, set: 2, 3 (in ya[0], ya[1]); both tails
+  if constexpr (ACC) {
+    asm volatile(WN_FOLD24_BODY
+                 "v_add_f32_dpp %[t0], %[t0], %[t2] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" "v_add_f32_dpp %[t1], %[t1], %[t3] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" "v_cndmask_b32_e64 %[t2], %[t1], %[t0], %[m0]\n\t" "v_cndmask_b32_e64 %[t3], %[t0], %[t1], %[m0]\n\t"
+                 "v_add_f32_dpp %[ya2], %[ya2], %[ya3] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" "v_add_f32_dpp %[t0], %[t2], %[t3] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" "v_add_f32 %[acc], %[acc], %[t0]\n\t" "v_add_f32_dpp %[ya2], %[ya2], %[ya2] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1"
+                 : [ya0] "=&v"(ya[0]), [ya1] "=&v"(ya[1]), [ya2] "=&v"(ya[2]), [ya3] "=&v"(ya[3]), [t0] "=&v"(t[0]), [t1] "=&v"(t[1]), [t2] "=&v"(t[2]), [t3] "=&v"(t[3]), [acc] "+v"(r16)
+                 : [z0] "v"(y[0]), [z1] "v"(y[1]), [z2] "v"(y[2]), [z3] "v"(y[3]), [x16] "v"(x[16]), [x17] "v"(x[17]), [x18] "v"(x[18]), [x19] "v"(x[19]), [x20] "v"(x[20]), [x21] "v"(x[21]), [x22] "v"(x[22]), [x23] "v"(x[23]), [m1] "s"(m1), [m0] "s"(m0));
+  } else {
+    asm volatile(WN_FOLD24_BODY
+                 "v_add_f32_dpp %[t0], %[t0], %[t2] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" "v_add_f32_dpp %[t1], %[t1], %[t3] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" "v_add_f32_dpp %[ya2], %[ya2], %[ya3] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" "v_cndmask_b32_e64 %[t2], %[t1], %[t0], %[m0]\n\t"
+                 "v_cndmask_b32_e64 %[t3], %[t0], %[t1], %[m0]\n\t" "v_add_f32_dpp %[ya2], %[ya2], %[ya2] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" "v_add_f32_dpp %[t0], %[t2], %[t3] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1"
+                 : [ya0] "=&v"(ya[0]), [ya1] "=&v"(ya[1]), [ya2] "=&v"(ya[2]), [ya3] "=&v"(ya[3]), [t0] "=&v"(t[0]), [t1] "=&v"(t[1]), [t2] "=&v"(t[2]), [t3] "=&v"(t[3])
+                 : [z0] "v"(y[0]), [z1] "v"(y[1]), [z2] "v"(y[2]), [z3] "v"(y[3]), [x16] "v"(x[16]), [x17] "v"(x[17]), [x18] "v"(x[18]), [x19] "v"(x[19]), [x20] "v"(x[20]), [x21] "v"(x[21]), [x22] "v"(x[22]), [x23] "v"(x[23]), [m1] "s"(m1), [m0] "s"(m0));
+    r16 = t[0];
+  }
+  r8 = ya[2];
+}
+#undef WN_FOLD24_BODY
+// The 24 products J^[k] * m (prod(k, m): the pair 2k, 2k + 1) in the order wn_fold24 needs: pairs 0 and 4 (x[0], x[8]: its first reads) first, the ten
+// others behind an empty statement that takes those two and m — they depend on it, so they stand between —, and pairs 8 .. 11 complete in front of it
+typedef float wn_v2f __attribute__((ext_vector_type(2)));
+template <class PROD> DEV void wn_products24(float* p, float m, PROD prod) {
+  wn_v2f pr[12];
+  pr[0] = prod(0, m); pr[4] = prod(4, m);
+  asm volatile("" : "+v"(pr[0]), "+v"(pr[4]), "+v"(m));
+#pragma unroll
+  for (int k = 1; k < 12; k++) if (k != 4) pr[k] = prod(k, m);
+  asm volatile("" : "+v"(pr[8]), "+v"(pr[9]), "+v"(pr[10]), "+v"(pr[11]));
+#pragma unroll
+  for (int k = 0; k < 12; k++) { p[2 * k] = pr[k].x; p[2 * k + 1] = pr[k].y; }
 }
 // sum over the 16 lanes of a row, result in every lane of the row (integers: order-independent)
 DEV int wn_rowsum_i(int v) {
@@ -80,41 +124,59 @@ DEV float wn_rowsum_f(float v) {
 
 // u = J^ . a^ : a_lo / a_hi hold the dof vector (lane q of the row: dofs q and 16 + q); two independent chains
 #define WN_FM(acc, x, y, R) "v_fmac_f32_dpp " acc ", " x ", " y " row_newbcast:" #R " row_mask:0xf bank_mask:0xf\n\t"
-template <int NV> DEV float wn_dot(const float* J, const float a_lo, const float a_hi) {
+// (24 slots: ONE statement, a_lo's sixteen multiply-adds first.  Statements carry a wait state only where a hazard exists — a VALU write of a DPP-read
+//  register within the two instructions in front of the read; tests/test_window_wait_states.py walks the listing for it.  a_hi is read behind the sixteen
+//  instructions of the a_lo chain whatever stands in front of the statement.  GUARD = false is for the sweeps, where a_lo is formed two instructions in
+//  front of the dot by construction: inside wn_fold24<true> (16-row forms), inside wn_rows4_sum2_acc (64-row form) and wn_jt32's statement (32-row
+//  form), each time followed by one more instruction of that statement and the a_hi accumulation.  GUARD = true: every other caller — two wait states
+//  in front, a_lo may be fresh or a copy.)
+#define WN_DOT24(guard) asm volatile(guard "v_mul_f32_dpp %0, %2, %4 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t" \
+               WN_FM("%0", "%2", "%5", 1) WN_FM("%0", "%2", "%6", 2) WN_FM("%0", "%2", "%7", 3) WN_FM("%0", "%2", "%8", 4) WN_FM("%0", "%2", "%9", 5) \
+               WN_FM("%0", "%2", "%10", 6) WN_FM("%0", "%2", "%11", 7) WN_FM("%0", "%2", "%12", 8) WN_FM("%0", "%2", "%13", 9) WN_FM("%0", "%2", "%14", 10) \
+               WN_FM("%0", "%2", "%15", 11) WN_FM("%0", "%2", "%16", 12) WN_FM("%0", "%2", "%17", 13) WN_FM("%0", "%2", "%18", 14) WN_FM("%0", "%2", "%19", 15) \
+               "v_mul_f32_dpp %1, %3, %20 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t" \
+               WN_FM("%1", "%3", "%21", 2) WN_FM("%1", "%3", "%22", 4) WN_FM("%1", "%3", "%23", 6) WN_FM("%1", "%3", "%24", 8) WN_FM("%1", "%3", "%25", 10) \
+               WN_FM("%1", "%3", "%26", 12) WN_FM("%1", "%3", "%27", 14) \
+               : "=&v"(u0), "=&v"(u1) : "v"(a_lo), "v"(a_hi), "v"(J[0]), "v"(J[1]), "v"(J[2]), "v"(J[3]), "v"(J[4]), "v"(J[5]), "v"(J[6]), "v"(J[7]), \
+                 "v"(J[8]), "v"(J[9]), "v"(J[10]), "v"(J[11]), "v"(J[12]), "v"(J[13]), "v"(J[14]), "v"(J[15]), \
+                 "v"(J[16]), "v"(J[17]), "v"(J[18]), "v"(J[19]), "v"(J[20]), "v"(J[21]), "v"(J[22]), "v"(J[23]))
+template <int NV, bool GUARD = true> DEV float wn_dot(const float* J, const float a_lo, const float a_hi) {
   static_assert(NV == 24 || NV == 32, "window kernel instances: 24 or 32 dof slots");
   float u0, u1;
-  asm volatile("s_nop 1\n\tv_mul_f32_dpp %0, %1, %2 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"
-               WN_FM("%0", "%1", "%3", 1) WN_FM("%0", "%1", "%4", 2) WN_FM("%0", "%1", "%5", 3) WN_FM("%0", "%1", "%6", 4) WN_FM("%0", "%1", "%7", 5)
-               WN_FM("%0", "%1", "%8", 6) WN_FM("%0", "%1", "%9", 7) WN_FM("%0", "%1", "%10", 8) WN_FM("%0", "%1", "%11", 9) WN_FM("%0", "%1", "%12", 10)
-               WN_FM("%0", "%1", "%13", 11) WN_FM("%0", "%1", "%14", 12) WN_FM("%0", "%1", "%15", 13) WN_FM("%0", "%1", "%16", 14) WN_FM("%0", "%1", "%17", 15)
-               : "=&v"(u0) : "v"(a_lo), "v"(J[0]), "v"(J[1]), "v"(J[2]), "v"(J[3]), "v"(J[4]), "v"(J[5]), "v"(J[6]), "v"(J[7]),
-                 "v"(J[8]), "v"(J[9]), "v"(J[10]), "v"(J[11]), "v"(J[12]), "v"(J[13]), "v"(J[14]), "v"(J[15]));
-  if constexpr (NV == 24)      // (a_hi: lane 2j carries dof 16 + j — wn_fold8)
+  if constexpr (NV == 24) {      // (a_hi: lane 2j carries dof 16 + j)
+    if constexpr (GUARD) WN_DOT24("s_nop 1\n\t"); else WN_DOT24("");
+  } else {
     asm volatile("s_nop 1\n\tv_mul_f32_dpp %0, %1, %2 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"
-                 WN_FM("%0", "%1", "%3", 2) WN_FM("%0", "%1", "%4", 4) WN_FM("%0", "%1", "%5", 6) WN_FM("%0", "%1", "%6", 8) WN_FM("%0", "%1", "%7", 10)
-                 WN_FM("%0", "%1", "%8", 12) WN_FM("%0", "%1", "%9", 14)
-                 : "=&v"(u1) : "v"(a_hi), "v"(J[16]), "v"(J[17]), "v"(J[18]), "v"(J[19]), "v"(J[20]), "v"(J[21]), "v"(J[22]), "v"(J[23]));
-  else
+                 WN_FM("%0", "%1", "%3", 1) WN_FM("%0", "%1", "%4", 2) WN_FM("%0", "%1", "%5", 3) WN_FM("%0", "%1", "%6", 4) WN_FM("%0", "%1", "%7", 5)
+                 WN_FM("%0", "%1", "%8", 6) WN_FM("%0", "%1", "%9", 7) WN_FM("%0", "%1", "%10", 8) WN_FM("%0", "%1", "%11", 9) WN_FM("%0", "%1", "%12", 10)
+                 WN_FM("%0", "%1", "%13", 11) WN_FM("%0", "%1", "%14", 12) WN_FM("%0", "%1", "%15", 13) WN_FM("%0", "%1", "%16", 14) WN_FM("%0", "%1", "%17", 15)
+                 : "=&v"(u0) : "v"(a_lo), "v"(J[0]), "v"(J[1]), "v"(J[2]), "v"(J[3]), "v"(J[4]), "v"(J[5]), "v"(J[6]), "v"(J[7]),
+                   "v"(J[8]), "v"(J[9]), "v"(J[10]), "v"(J[11]), "v"(J[12]), "v"(J[13]), "v"(J[14]), "v"(J[15]));
     asm volatile("s_nop 1\n\tv_mul_f32_dpp %0, %1, %2 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"
                  WN_FM("%0", "%1", "%3", 1) WN_FM("%0", "%1", "%4", 2) WN_FM("%0", "%1", "%5", 3) WN_FM("%0", "%1", "%6", 4) WN_FM("%0", "%1", "%7", 5)
                  WN_FM("%0", "%1", "%8", 6) WN_FM("%0", "%1", "%9", 7)
                  : "=&v"(u1) : "v"(a_hi), "v"(J[16]), "v"(J[17]), "v"(J[18]), "v"(J[19]), "v"(J[20]), "v"(J[21]), "v"(J[22]), "v"(J[23]));
-  if constexpr (NV == 32)
     asm volatile("s_nop 1\n\t" WN_FM("%0", "%1", "%2", 8) WN_FM("%0", "%1", "%3", 9) WN_FM("%0", "%1", "%4", 10) WN_FM("%0", "%1", "%5", 11)
                  WN_FM("%0", "%1", "%6", 12) WN_FM("%0", "%1", "%7", 13) WN_FM("%0", "%1", "%8", 14) WN_FM("%0", "%1", "%9", 15)
                  : "+v"(u1) : "v"(a_hi), "v"(J[NV == 32 ? 24 : 0]), "v"(J[NV == 32 ? 25 : 0]), "v"(J[NV == 32 ? 26 : 0]), "v"(J[NV == 32 ? 27 : 0]),
                    "v"(J[NV == 32 ? 28 : 0]), "v"(J[NV == 32 ? 29 : 0]), "v"(J[NV == 32 ? 30 : 0]), "v"(J[NV == 32 ? 31 : 0]));
+  }
   return u0 + u1;
 }
+#undef WN_DOT24
 // a^ += J^T x over the row's 16 lanes
 template <int NV> DEV void wn_jt(const float* J, const float x, float& a_lo, float& a_hi) {
   typedef float v2f __attribute__((ext_vector_type(2)));
-  const v2f x2 = {x, x};
   float p[NV];
+  if constexpr (NV == 32) {
+    const v2f x2 = {x, x};
 #pragma unroll
-  for (int k = 0; k < NV; k += 2) { const v2f pr = v2f{J[k], J[k + 1]} * x2; p[k] = pr.x; p[k + 1] = pr.y; }     // v_pk_mul_f32
-  a_lo += wn_fold16(p);
-  if constexpr (NV == 32) a_hi += wn_fold16(p + 16); else a_hi += wn_fold8(p + 16);
+    for (int k = 0; k < NV; k += 2) { const v2f pr = v2f{J[k], J[k + 1]} * x2; p[k] = pr.x; p[k + 1] = pr.y; }     // v_pk_mul_f32
+    a_lo += wn_fold16(p); a_hi += wn_fold16(p + 16);
+  } else {
+    wn_products24(p, x, [&](const int k, const float m) __attribute__((always_inline)) { return v2f{J[2 * k], J[2 * k + 1]} * v2f{m, m}; });
+    float s8; wn_fold24<true>(p, a_lo, s8); a_hi += s8;
+  }
 }
 
 
@@ -139,17 +201,19 @@ struct WnWin32 { float J[24]; float4 A0, A1, A2, A3, C0, C1, C2, C3; float aref,
 
 DEV void wn_jt32(const float* J, const float x, float& a_lo, float& a_hi) {
   typedef float v2f __attribute__((ext_vector_type(2)));
-  const v2f x2 = {x, x};
   float p[24];
-#pragma unroll
-  for (int k = 0; k < 24; k += 2) { const v2f pr = v2f{J[k], J[k + 1]} * x2; p[k] = pr.x; p[k + 1] = pr.y; }
-  float s_lo = wn_fold16(p), s_hi = wn_fold8(p + 16);
+  wn_products24(p, x, [&](const int k, const float m) __attribute__((always_inline)) { return v2f{J[2 * k], J[2 * k + 1]} * v2f{m, m}; });
+  float s_lo, s_hi;
+  wn_fold24<false>(p, s_lo, s_hi);
   // + the other half's 16 rows: v_permlane16_swap exchanges the odd 16-lane rows of the first register with the even rows of the second,
   // so (x, y) = (lower half's sum, upper half's sum) in EVERY lane afterwards: the same sum, in the same order, in both halves
   // (a VALU instruction: the LDS crossbar's round trip — ds_swizzle — sat three times in every window-sweep's chain)
-  float y_lo = s_lo, y_hi = s_hi;
-  asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %2\n\tv_permlane16_swap_b32 %1, %3\n\ts_nop 1" : "+v"(s_lo), "+v"(s_hi), "+v"(y_lo), "+v"(y_hi));
-  a_lo += s_lo + y_lo; a_hi += s_hi + y_hi;
+  // (two wait states in FRONT of a swap that reads a fresh VALU result — the second copy and `s_nop 0`, that nop and the first swap —, none behind
+  //  it where plain VALU instructions read its result; the accumulations inside, a_lo's first: two instructions behind it in the statement)
+  float y_lo, y_hi;
+  asm volatile("v_mov_b32 %2, %0\n\tv_mov_b32 %3, %1\n\ts_nop 0\n\tv_permlane16_swap_b32 %0, %2\n\tv_permlane16_swap_b32 %1, %3\n\t"
+               "v_add_f32 %0, %0, %2\n\tv_add_f32 %4, %4, %0\n\tv_add_f32 %1, %1, %3\n\tv_add_f32 %5, %5, %1"
+               : "+v"(s_lo), "+v"(s_hi), "=&v"(y_lo), "=&v"(y_hi), "+v"(a_lo), "+v"(a_hi));
 }
 
 // one hand-over row (window_pgs.h: WN_NK floats, sparse — a contact row touches at most two free bodies) expanded into the dense J^ over the
@@ -356,7 +420,7 @@ DEV void wn_run32(const DConst* __restrict__ C, const DState& S, const int env0,
     if (act) {
       int impl = 0;
       WN32_FOR_WINDOWS({
-        const float u = wn_dot<NV>(W.J, a_lo, a_hi);
+        const float u = wn_dot<NV, false>(W.J, a_lo, a_hi);
         const float fo = fw;
         float tt = ((u - W.aref) + W.R * fo) * W.nw;
         const float nf = -fo;
@@ -366,6 +430,7 @@ DEV void wn_run32(const DConst* __restrict__ C, const DState& S, const int env0,
         asm volatile("v_max_f32 %0, %1, %2" : "=v"(dl) : "v"(tt), "v"(nf));
         // ... their deltas reach the upper half through the cross tile ...
         float dx = dl, dy = dl;                                         // (dx: the lower half's deltas in the upper half's lanes)
+        // (both wait states are hazards: dx, dy are copies written right in front of the swap, and the cross multiply-adds read dx through the DPP network)
         asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 1" : "+v"(dx), "+v"(dy));
         WN_CROSS4(0, 1, 2, 3, W.C0); WN_CROSS4(4, 5, 6, 7, W.C1); WN_CROSS4(8, 9, 10, 11, W.C2); WN_CROSS4(12, 13, 14, 15, W.C3);
         // ... rows 16..31 (upper half)
@@ -400,23 +465,34 @@ DEV float* wn_lds_base() { return wn_lds; }
 struct WnWin64 { float J[24]; float A[64]; float aref, R, nw, half; };
 
 // sum over the four 16-lane rows of a wavefront, the same value (same order of additions) in every lane
+// (ONE statement.  A swap needs two wait states between a VALU write of either operand and itself and none behind it where a plain VALU
+//  instruction reads its result — what the compiler emits around __builtin_amdgcn_permlane16_swap, profiles/window_slots_summary.md.  The two copies
+//  stand inside: the second copy and one `s_nop 0` are the first swap's two states, that nop and the first swap the second swap's.)
 DEV void wn_rows4_sum2(float& x, float& y) {
-  float x2 = x, y2 = y;
-  asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %2\n\tv_permlane16_swap_b32 %1, %3\n\ts_nop 1" : "+v"(x), "+v"(y), "+v"(x2), "+v"(y2));
-  x += x2; y += y2;                       // rows 0, 1: r0 + r1; rows 2, 3: r2 + r3
-  x2 = x; y2 = y;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %2\n\tv_permlane32_swap_b32 %1, %3\n\ts_nop 1" : "+v"(x), "+v"(y), "+v"(x2), "+v"(y2));
-  x += x2; y += y2;                       // (r0 + r1) + (r2 + r3) everywhere
+  float x2, y2;
+  asm volatile("v_mov_b32 %2, %0\n\tv_mov_b32 %3, %1\n\ts_nop 0\n\tv_permlane16_swap_b32 %0, %2\n\tv_permlane16_swap_b32 %1, %3\n\t"
+               "v_add_f32 %0, %0, %2\n\tv_add_f32 %1, %1, %3\n\t"                       // rows 0, 1: r0 + r1; rows 2, 3: r2 + r3
+               "v_mov_b32 %2, %0\n\tv_mov_b32 %3, %1\n\ts_nop 0\n\tv_permlane32_swap_b32 %0, %2\n\tv_permlane32_swap_b32 %1, %3\n\t"
+               "v_add_f32 %0, %0, %2\n\tv_add_f32 %1, %1, %3"                             // (r0 + r1) + (r2 + r3) everywhere
+               : "+v"(x), "+v"(y), "=&v"(x2), "=&v"(y2));
+}
+// ... and a_lo += x, a_hi += y inside the statement, a_lo's first: `y + y2` and the a_hi accumulation are the two instructions between the write of
+// a_lo and the next dot's first DPP read of it (wn_dot<NV, false>), whatever the compiler puts around the statement
+DEV void wn_rows4_sum2_acc(float x, float y, float& a_lo, float& a_hi) {
+  float x2, y2;
+  asm volatile("v_mov_b32 %2, %0\n\tv_mov_b32 %3, %1\n\ts_nop 0\n\tv_permlane16_swap_b32 %0, %2\n\tv_permlane16_swap_b32 %1, %3\n\t"
+               "v_add_f32 %0, %0, %2\n\tv_add_f32 %1, %1, %3\n\t"
+               "v_mov_b32 %2, %0\n\tv_mov_b32 %3, %1\n\ts_nop 0\n\tv_permlane32_swap_b32 %0, %2\n\tv_permlane32_swap_b32 %1, %3\n\t"
+               "v_add_f32 %0, %0, %2\n\tv_add_f32 %4, %4, %0\n\tv_add_f32 %1, %1, %3\n\tv_add_f32 %5, %5, %1"
+               : "+v"(x), "+v"(y), "=&v"(x2), "=&v"(y2), "+v"(a_lo), "+v"(a_hi));
 }
 DEV void wn_jt64(const float* J, const float x, float& a_lo, float& a_hi) {
   typedef float v2f __attribute__((ext_vector_type(2)));
-  const v2f x2 = {x, x};
   float p[24];
-#pragma unroll
-  for (int k = 0; k < 24; k += 2) { const v2f pr = v2f{J[k], J[k + 1]} * x2; p[k] = pr.x; p[k + 1] = pr.y; }
-  float s_lo = wn_fold16(p), s_hi = wn_fold8(p + 16);
-  wn_rows4_sum2(s_lo, s_hi);
-  a_lo += s_lo; a_hi += s_hi;
+  wn_products24(p, x, [&](const int k, const float m) __attribute__((always_inline)) { return v2f{J[2 * k], J[2 * k + 1]} * v2f{m, m}; });
+  float s_lo, s_hi;
+  wn_fold24<false>(p, s_lo, s_hi);
+  wn_rows4_sum2_acc(s_lo, s_hi, a_lo, a_hi);
 }
 // one 16-lane row's 16 constraint rows (lanes of DPP row mask m): per row  v_max, two wait states, v_fmac ... row_newbcast — the 16-row form's chain
 // (ONE statement per chain, the closing v_max included: between two statements the compiler cannot see that `v_fmac ... dpp t` -> `v_max d, t` needs no
@@ -427,42 +503,44 @@ DEV void wn_jt64(const float* J, const float x, float& a_lo, float& a_hi) {
     "v_max_f32 %[d], %[t], %[nf]" \
     : [t] "+v"(tt), [d] "=&v"(dl) : [nf] "v"(nf), [a0] "v"(A[b]), [a1] "v"(A[b + 1]), [a2] "v"(A[b + 2]), [a3] "v"(A[b + 3]), [a4] "v"(A[b + 4]), [a5] "v"(A[b + 5]), [a6] "v"(A[b + 6]), [a7] "v"(A[b + 7]), \
       [a8] "v"(A[b + 8]), [a9] "v"(A[b + 9]), [a10] "v"(A[b + 10]), [a11] "v"(A[b + 11]), [a12] "v"(A[b + 12]), [a13] "v"(A[b + 13]), [a14] "v"(A[b + 14]), [a15] "v"(A[b + 15]))
-// the deltas dx of a finished 16-lane row (replicated into every row) reach the rows behind it (mask m) through their cross entries
-#define WN64_XF(r, ar, m) "v_fmac_f32_dpp %[t], %[x], " ar " row_newbcast:" #r " row_mask:" #m " bank_mask:0xf\n\t"
-#define WN64_X4(r0, r1, r2, r3, a0_, a1_, a2_, a3_, m) asm volatile(WN64_XF(r0, "%[a0]", m) WN64_XF(r1, "%[a1]", m) WN64_XF(r2, "%[a2]", m) WN64_XF(r3, "%[a3]", m) \
-    : [t] "+v"(tt) : [x] "v"(dx), [a0] "v"(a0_), [a1] "v"(a1_), [a2] "v"(a2_), [a3] "v"(a3_))
-#define WN64_CROSS16(A, b, m) do { WN64_X4(0, 1, 2, 3, A[b], A[b + 1], A[b + 2], A[b + 3], m); WN64_X4(4, 5, 6, 7, A[b + 4], A[b + 5], A[b + 6], A[b + 7], m); \
-    WN64_X4(8, 9, 10, 11, A[b + 8], A[b + 9], A[b + 10], A[b + 11], m); WN64_X4(12, 13, 14, 15, A[b + 12], A[b + 13], A[b + 14], A[b + 15], m); } while (0)
+// A finished 16-lane row's deltas, replicated into every row by lane swaps, and their 16 cross multiply-adds into the rows of mask m: ONE statement
+// (between two statements the compiler puts an `s_nop 0`; four cross statements and two swap statements were six seams per row).  The swaps work on
+// the chain's own d (it is formed again by the next chain's first v_max): one copy in front of each swap, two wait states between that copy and the
+// swap, none behind a swap whose result a plain v_mov reads, two in front of the first cross multiply-add (a DPP read of the last swap's result).
+//   row 0: x = (d0, d0, d0, d0);  row 1: y = (d1, d1, d1, d1);  row 2: d = (., ., d2, d2)
+#define WN64_XFS(src, r, ar, m) "v_fmac_f32_dpp %[t], " src ", " ar " row_newbcast:" #r " row_mask:" #m " bank_mask:0xf\n\t"
+#define WN64_XF16(src, m) WN64_XFS(src, 0, "%[a0]", m) WN64_XFS(src, 1, "%[a1]", m) WN64_XFS(src, 2, "%[a2]", m) WN64_XFS(src, 3, "%[a3]", m) WN64_XFS(src, 4, "%[a4]", m) WN64_XFS(src, 5, "%[a5]", m) \
+    WN64_XFS(src, 6, "%[a6]", m) WN64_XFS(src, 7, "%[a7]", m) WN64_XFS(src, 8, "%[a8]", m) WN64_XFS(src, 9, "%[a9]", m) WN64_XFS(src, 10, "%[a10]", m) WN64_XFS(src, 11, "%[a11]", m) \
+    WN64_XFS(src, 12, "%[a12]", m) WN64_XFS(src, 13, "%[a13]", m) WN64_XFS(src, 14, "%[a14]", m) "v_fmac_f32_dpp %[t], " src ", %[a15] row_newbcast:15 row_mask:" #m " bank_mask:0xf"
+#define WN64_A16(A, b) [a0] "v"(A[b]), [a1] "v"(A[b + 1]), [a2] "v"(A[b + 2]), [a3] "v"(A[b + 3]), [a4] "v"(A[b + 4]), [a5] "v"(A[b + 5]), [a6] "v"(A[b + 6]), [a7] "v"(A[b + 7]), \
+    [a8] "v"(A[b + 8]), [a9] "v"(A[b + 9]), [a10] "v"(A[b + 10]), [a11] "v"(A[b + 11]), [a12] "v"(A[b + 12]), [a13] "v"(A[b + 13]), [a14] "v"(A[b + 14]), [a15] "v"(A[b + 15])
+#define WN64_BCAST_X0(A, b, m) asm volatile("v_mov_b32 %[y], %[d]\n\ts_nop 1\n\tv_permlane16_swap_b32 %[d], %[y]\n\t"       /* d = (d0, d0, ., .) */ \
+    "v_mov_b32 %[x], %[d]\n\ts_nop 1\n\tv_permlane32_swap_b32 %[x], %[d]\n\ts_nop 1\n\t"                                   /* x = (d0, d0, d0, d0) */ \
+    WN64_XF16("%[x]", m) : [t] "+v"(tt), [d] "+v"(dl), [x] "=&v"(dx), [y] "=&v"(dy) : WN64_A16(A, b))
+#define WN64_BCAST_X1(A, b, m) asm volatile("v_mov_b32 %[y], %[d]\n\ts_nop 1\n\tv_permlane16_swap_b32 %[d], %[y]\n\t"       /* y = (d1, d1, ., .) */ \
+    "v_mov_b32 %[x], %[y]\n\ts_nop 1\n\tv_permlane32_swap_b32 %[y], %[x]\n\ts_nop 1\n\t"                                   /* y = (d1, d1, d1, d1) */ \
+    WN64_XF16("%[y]", m) : [t] "+v"(tt), [d] "+v"(dl), [x] "=&v"(dx), [y] "=&v"(dy) : WN64_A16(A, b))
+#define WN64_BCAST_X2(A, b, m) asm volatile("v_mov_b32 %[y], %[d]\n\ts_nop 1\n\tv_permlane16_swap_b32 %[d], %[y]\n\ts_nop 1\n\t"       /* d = (., ., d2, d2) */ \
+    WN64_XF16("%[d]", m) : [t] "+v"(tt), [d] "+v"(dl), [y] "=&v"(dy) : WN64_A16(A, b))
 // one sweep over a 64-row window: u = J^ a^, then the four 16-lane rows one after the other (Gauss-Seidel row by row inside each: DPP row
 // masks 0x1 .. 0x8), the deltas of a finished row carried to every later row by two lane swaps and 16 broadcast multiply-adds
 // (A: the tile array, Bg: index of the 16 entries of lane row g in it, Lg: statement in front of row g — the register-resident windows read
 //  W.A[16 g ..], the LDS window loads the 16 entries of row g first)
 #define WN64_SWEEP_X(W, fw, A, B0, B1, B2, B3, L0, L1, L2, L3) do { \
-    const float u = wn_dot<NV>(W.J, a_lo, a_hi); \
+    const float u = wn_dot<NV, false>(W.J, a_lo, a_hi); \
     const float fo = fw; \
     float tt = ((u - W.aref) + W.R * fo) * W.nw; \
     const float nf = -fo; \
     float dl, dx, dy; \
     L0; \
     WN64_CHAIN16(A, B0, 0x1); \
-    dx = dl; dy = dl; \
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 1" : "+v"(dx), "+v"(dy));        /* dx = (d0, d0, ., .) */ \
-    dy = dx; \
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(dx), "+v"(dy));        /* dx = (d0, d0, d0, d0) */ \
-    WN64_CROSS16(A, B0, 0xe); \
+    WN64_BCAST_X0(A, B0, 0xe); \
     L1; \
     WN64_CHAIN16(A, B1, 0x2); \
-    dx = dl; dy = dl; \
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 1" : "+v"(dx), "+v"(dy));        /* dy = (d1, d1, ., .) */ \
-    dx = dy; \
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(dy), "+v"(dx));        /* dy = (d1, d1, d1, d1) */ \
-    dx = dy; \
-    WN64_CROSS16(A, B1, 0xc); \
+    WN64_BCAST_X1(A, B1, 0xc); \
     L2; \
     WN64_CHAIN16(A, B2, 0x4); \
-    dx = dl; dy = dl; \
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 1" : "+v"(dx), "+v"(dy));        /* dx = (., ., d2, d2) */ \
-    WN64_CROSS16(A, B2, 0x8); \
+    WN64_BCAST_X2(A, B2, 0x8); \
     L3; \
     WN64_CHAIN16(A, B3, 0x8); \
     impl += imp_fixed((W.half * dl) * (2.0f * tt - dl), iq.qs); \
@@ -485,29 +563,19 @@ DEV void wn_jt64(const float* J, const float x, float& a_lo, float& a_hi) {
     WN64_R8F(0, 1, 2, 3, 4, 5, 6, 7, A, b, bc, m, mc, xp_, ""); \
     WN64_R8F(8, 9, 10, 11, 12, 13, 14, 15, A, b, bc, m, mc, xp_, "v_max_f32 %[d], %[t], %[nf]"); } while (0)
 #define WN64_SWEEP_F(W, fw) do { \
-    const float u = wn_dot<NV>(W.J, a_lo, a_hi); \
+    const float u = wn_dot<NV, false>(W.J, a_lo, a_hi); \
     const float fo = fw; \
     float tt = ((u - W.aref) + W.R * fo) * W.nw; \
     const float nf = -fo; \
     float dl, dx, dy, dx0, dx1; \
     WN64_CHAIN16(W.A, 0, 0x1); \
-    dx = dl; dy = dl; \
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 1" : "+v"(dx), "+v"(dy));        /* dx = (d0, d0, ., .) */ \
-    dy = dx; \
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(dx), "+v"(dy));        /* dx = (d0, d0, d0, d0) */ \
+    WN64_BCAST_X0(W.A, 0, 0x2);                                 /* row 0's deltas -> row 1 (now) */ \
     dx0 = dx; \
-    WN64_CROSS16(W.A, 0, 0x2);                                  /* row 0's deltas -> row 1 (now) */ \
     WN64_CHAIN16F(W.A, 16, 0x2, 0, 0xc, dx0);                   /* row 1's chain; in its wait slots: row 0's deltas -> rows 2, 3 */ \
-    dx = dl; dy = dl; \
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 1" : "+v"(dx), "+v"(dy));        /* dy = (d1, d1, ., .) */ \
-    dx = dy; \
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(dy), "+v"(dx));        /* dy = (d1, d1, d1, d1) */ \
-    dx = dy; dx1 = dy; \
-    WN64_CROSS16(W.A, 16, 0x4);                                 /* row 1's deltas -> row 2 (now) */ \
+    WN64_BCAST_X1(W.A, 16, 0x4);                                /* row 1's deltas -> row 2 (now) */ \
+    dx1 = dy; \
     WN64_CHAIN16F(W.A, 32, 0x4, 16, 0x8, dx1);                  /* row 2's chain; in its wait slots: row 1's deltas -> row 3 */ \
-    dx = dl; dy = dl; \
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 1" : "+v"(dx), "+v"(dy));        /* dx = (., ., d2, d2) */ \
-    WN64_CROSS16(W.A, 32, 0x8); \
+    WN64_BCAST_X2(W.A, 32, 0x8); \
     WN64_CHAIN16(W.A, 48, 0x8); \
     impl += imp_fixed((W.half * dl) * (2.0f * tt - dl), iq.qs); \
     fw = fo + dl; \
@@ -678,13 +746,17 @@ template <int NV> DEV void wn_jt2(const float* JA, const float xa, const float* 
   typedef float v2f __attribute__((ext_vector_type(2)));
   const v2f xa2 = {xa, xa}, xb2 = {xb, xb};
   float p[NV];
+  if constexpr (NV == 32) {
 #pragma unroll
-  for (int k = 0; k < NV; k += 2) {
-    const v2f pr = __builtin_elementwise_fma(v2f{JB[k], JB[k + 1]}, xb2, v2f{JA[k], JA[k + 1]} * xa2);     // v_pk_mul_f32, v_pk_fma_f32
-    p[k] = pr.x; p[k + 1] = pr.y;
+    for (int k = 0; k < NV; k += 2) {
+      const v2f pr = __builtin_elementwise_fma(v2f{JB[k], JB[k + 1]}, xb2, v2f{JA[k], JA[k + 1]} * xa2);     // v_pk_mul_f32, v_pk_fma_f32
+      p[k] = pr.x; p[k + 1] = pr.y;
+    }
+    a_lo += wn_fold16(p); a_hi += wn_fold16(p + 16);
+  } else {
+    wn_products24(p, xb, [&](const int k, const float m) __attribute__((always_inline)) { return __builtin_elementwise_fma(v2f{JB[2 * k], JB[2 * k + 1]}, v2f{m, m}, v2f{JA[2 * k], JA[2 * k + 1]} * xa2); });
+    float s8; wn_fold24<true>(p, a_lo, s8); a_hi += s8;
   }
-  a_lo += wn_fold16(p);
-  if constexpr (NV == 32) a_hi += wn_fold16(p + 16); else a_hi += wn_fold8(p + 16);
 }
 #define WN_XFMA(r, ar) "v_fmac_f32_dpp %[t], %[x], " ar " row_newbcast:" #r " row_mask:0xf bank_mask:0xf\n\t"
 #define WN_CROSS4A(r0, r1, r2, r3, T) asm volatile(WN_XFMA(r0, "%[a0]") WN_XFMA(r1, "%[a1]") WN_XFMA(r2, "%[a2]") WN_XFMA(r3, "%[a3]") \
@@ -781,7 +853,7 @@ __global__ __launch_bounds__(64, 1) void mjh_window_kernel(const DConst* __restr
   const int nwin = (nrow + 15) >> 4;
   const int nwmax = max(max(__builtin_amdgcn_readlane(nwin, 0), __builtin_amdgcn_readlane(nwin, 16)), max(__builtin_amdgcn_readlane(nwin, 32), __builtin_amdgcn_readlane(nwin, 48)));
   const int nv = M.nv;
-  // dof vectors: lane q of the row carries dof q (lo) and dof 16 + q (hi; the 24-slot instance: dof 16 + (q >> 1), wn_fold8)
+  // dof vectors: lane q of the row carries dof q (lo) and dof 16 + q (hi; the 24-slot instance: dof 16 + (q >> 1), wn_fold24)
   const int dhi = NV == 24 ? 16 + (q >> 1) : 16 + q;
   const bool lo_on = q < nv, hi_on = dhi < nv;
   const float as_lo = lo_on ? wb[WN_AS + q] : 0.0f, as_hi = hi_on ? wb[WN_AS + dhi] : 0.0f;
@@ -943,9 +1015,9 @@ __global__ __launch_bounds__(64, 1) void mjh_window_kernel(const DConst* __restr
   auto sweep_pair_fill = [&](WnWin<NV>& A, WnWin<NV>& B, const float4& X0, const float4& X1, const float4& X2, const float4& X3, float& fa, float& fb) __attribute__((always_inline)) {
     if constexpr (NV == 24) {
       typedef float v2f __attribute__((ext_vector_type(2)));
-      const float ua = wn_dot<NV>(A.J, a_lo, a_hi);
+      const float ua = wn_dot<NV, false>(A.J, a_lo, a_hi);
       float ub1;                                   // window B's dot over dofs 16 .. 23 (a_hi: lane 2j carries dof 16 + j)
-      asm volatile("s_nop 1\n\tv_mul_f32_dpp %0, %1, %2 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"
+      asm volatile("v_mul_f32_dpp %0, %1, %2 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"      // (no wait state: a_hi is what the dot above has read)
                    WN_FM("%0", "%1", "%3", 2) WN_FM("%0", "%1", "%4", 4) WN_FM("%0", "%1", "%5", 6) WN_FM("%0", "%1", "%6", 8) WN_FM("%0", "%1", "%7", 10)
                    WN_FM("%0", "%1", "%8", 12) WN_FM("%0", "%1", "%9", 14)
                    : "=&v"(ub1) : "v"(a_hi), "v"(B.J[16]), "v"(B.J[17]), "v"(B.J[18]), "v"(B.J[19]), "v"(B.J[20]), "v"(B.J[21]), "v"(B.J[22]), "v"(B.J[23]));
@@ -963,8 +1035,7 @@ __global__ __launch_bounds__(64, 1) void mjh_window_kernel(const DConst* __restr
       {
         const float ub = ub0 + ub1;
         float tt = ((ub - B.aref) + B.R * fob) * B.nw;
-        float dx = dla;
-        asm volatile("s_nop 1" : "+v"(dx));
+        const float dx = dla;            // (no wait state: the four instructions that form tt stand between the v_max that closed A's chain and the first read)
         WN_CROSS4A(0, 1, 2, 3, X0); WN_CROSS4A(4, 5, 6, 7, X1); WN_CROSS4A(8, 9, 10, 11, X2); WN_CROSS4A(12, 13, 14, 15, X3);
         const float nf = -fob;
         float dl;
@@ -976,18 +1047,17 @@ __global__ __launch_bounds__(64, 1) void mjh_window_kernel(const DConst* __restr
         fb = fob + dl; dlb = dl;
       }
       {   // a^ += J_A^T delta_A + J_B^T delta_B: A's products are there, B's join them, one transpose-reduce (wn_jt2)
-        const v2f xb2 = {dlb, dlb};
         float pp[NV];
-#pragma unroll
-        for (int k = 0; k < NV / 2; k++) { const v2f pr = __builtin_elementwise_fma(WN_J2(B.J, k), xb2, p[k]); pp[2 * k] = pr.x; pp[2 * k + 1] = pr.y; }
+        wn_products24(pp, dlb, [&](const int k, const float m) __attribute__((always_inline)) { return __builtin_elementwise_fma(WN_J2(B.J, k), v2f{m, m}, p[k]); });
 #undef WN_J2
-        a_lo += wn_fold16(pp);
-        a_hi += wn_fold8(pp + 16);
+        float s8;
+        wn_fold24<true>(pp, a_lo, s8);
+        a_hi += s8;
       }
     }
   };
 #define WN_SWEEP_ONE(W, fw) do { \
-    const float u = wn_dot<NV>(W.J, a_lo, a_hi); \
+    const float u = wn_dot<NV, false>(W.J, a_lo, a_hi); \
     const float fo = fw; \
     float tt = ((u - W.aref) + W.R * fo) * W.nw; \
     const float nf = -fo; \
