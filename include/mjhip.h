@@ -190,7 +190,20 @@ typedef struct mjh_model {
    * used.  0.5 0.5 0.5 1 unless set [UPSTREAM, unverified here: MuJoCo's geom default].  NULL in a model assembled from tables: every
    * geom has the default. */
   double* geom_rgba;                /* [4*ngeom] */
+  /* ---- appended for lights (older fields keep their offsets) ----
+   * <light mode="fixed">: a frame attached to a body.  mjh_render's colour image takes the active lights when the engine's lighting
+   * mode is 1 (mjh_render_set_lighting below, where the formula stands).  At most MJH_MAXLIGHT lights; a model assembled from tables
+   * has none.  specular and attenuation are not modelled. */
+  int nlight;
+  int* light_bodyid;                      /* [nlight] */
+  double *light_pos, *light_dir;          /* [3 nlight] each: position and unit direction in the body's frame */
+  int *light_directional, *light_castshadow, *light_active;   /* [nlight] each, 0 / 1 */
+  double *light_diffuse, *light_ambient;  /* [3 nlight] each: r, g, b, finite and not negative */
+  double *light_cutoff, *light_exponent;  /* [nlight] each: spot cone half-angle in degrees, (0, 180]; spot exponent >= 0 */
+  char** light_names;
 } mjh_model;
+
+#define MJH_MAXLIGHT 8   /* lights a model can hold (they travel to the light kernel in its arguments) */
 
 /* ------------------------------------------------- model builder (host) */
 /* Replaces the model-ingest boundary mj_loadXML (include/mujoco_sim/mj_util.h:190)
@@ -254,6 +267,15 @@ int mjh_builder_add_camera(mjh_builder*, const char* name, int body, const doubl
 /* <geom rgba>: the colour of geom `geom` (the id an mjh_builder_add_*geom call returned; the compiled model may number it differently,
  * the colour follows it).  A bad id, a NULL pointer or a component outside [0, 1]: MJH_ERR_ARG, nothing is changed. */
 int mjh_builder_set_geom_rgba(mjh_builder*, int geom, const double rgba[4]);
+/* <light> (fixed mode): returns the light id.  pos / dir in the body's frame; dir is normalised.  NULL pointers take the defaults
+ * [UPSTREAM, unverified here: MuJoCo's light defaults]: pos 0 0 0, dir 0 0 -1, diffuse 0.7 0.7 0.7, ambient 0 0 0; the XML defaults of
+ * the scalars are positional, castshadow on (directional / castshadow < 0 take them), cutoff 45 degrees and exponent 10 (given
+ * explicitly: the loader passes them).  The light is active.  A bad body, a zero
+ * or non-finite dir, a negative or non-finite colour component, cutoff outside (0, 180], a negative or non-finite exponent, or a light
+ * beyond MJH_MAXLIGHT: MJH_ERR_ARG, nothing is added.  Like a camera the light follows its body through the compile step's reordering. */
+int mjh_builder_add_light(mjh_builder*, const char* name, int body, const double pos[3], const double dir[3], int directional,
+                          int castshadow, const double diffuse[3], const double ambient[3], double cutoff_deg, double exponent);
+int mjh_builder_set_light_active(mjh_builder*, int light, int on);   /* <light active>: the model's light_active (a bad id: MJH_ERR_ARG) */
 /* compile: derives inertias, qpos0, invweight0, meaninertia, rbound, pair list */
 mjh_model* mjh_builder_compile(mjh_builder*);
 void mjh_model_destroy(mjh_model*);
@@ -266,7 +288,7 @@ void mjh_model_destroy(mjh_model*);
  * continue until the slowest instance has converged), `time`, the statistics row and the bad-state reset.  Contact
  * and row capacities scale with `copies`.  Returns a new model (mjh_model_destroy) or NULL. */
 mjh_model* mjh_model_replicate(const mjh_model* m, int copies);
-int mjh_name2id(const mjh_model*, int objtype /*0 body,1 joint,2 geom,3 site,4 sensor,5 camera*/, const char* name);
+int mjh_name2id(const mjh_model*, int objtype /*0 body,1 joint,2 geom,3 site,4 sensor,5 camera,6 light*/, const char* name);
 const char* mjh_id2name(const mjh_model*, int objtype, int id);
 
 /* MJCF-subset loader: replaces load_XML -> mj_loadXML (include/mujoco_sim/mj_util.h:185-193) for the element
@@ -578,6 +600,41 @@ int mjh_render_device(mjh_engine*, int env0, int n, const mjh_render_options*,
                       float* d_depth, int* d_geomid, float* d_normal /*[n][H][W][3]*/, unsigned char* d_rgba /*[n][H][W][4]*/);
 /* host pointers: calls the device form through the engine-owned staging buffer and synchronises */
 int mjh_render(mjh_engine*, int env0, int n, const mjh_render_options*, float* depth, int* geomid, float* normal, unsigned char* rgba);
+
+/* Lights and cast shadows in the colour image.  mjh_render_set_lighting(engine, mode): 0 (the default) is the call above — the same
+ * launches and the same bits whether or not the model has lights; 1: the colour image also takes the model's active lights.  Any other
+ * mode returns MJH_ERR_ARG and changes nothing.  Depth, geom id and normal are mode 0's bits in either mode.
+ *   Mode 1, a hit on geom g: channel c is level(rgba[g][c] * (shade + sum_l (amb_l[c] + dif_l[c] * t_l))) with shade = ambient +
+ *   diffuse |n . v^| as above, level(x) = (int)(255 min(1, x) + 0.5), the sum over the active lights in id order, in fp32; alpha 255;
+ *   a miss is the background.  With no active light the launches and the image are mode 0's.
+ *   Per light: h = p + x v is the hit point (p the camera origin, v the pixel's ray, x its parameter), n the pixel's normal as the
+ *   normal image holds it (towards the camera), L and d^ the light's position and unit direction in the world frame, from its body's
+ *   pose in that env.  l = -d^ for a directional light, L - h for a positional one; l^ = l / |l|.
+ *     t_l = max(0, n . l^) * spot * lit
+ *     spot (positional lights only; 1 for directional ones): with c = -l^ . d^, c^exponent if c >= cos(cutoff), else 0
+ *     lit = 0 if options.shadows, the light has castshadow, n . l^ > 0 and the shadow ray is blocked; else 1
+ *   The shadow ray starts at o = h + bias n.  Directional light: direction -d^, unbounded.  Positional light: direction L - o, blocked
+ *   only by a hit with ray parameter < 1 (a geom beyond the light blocks nothing).  It sees exactly the geoms the image's own rays
+ *   see: bodyexclude, flg_static = 0, an inactive slot, mesh mode and mesh surface hide a geom from the shadow ray too, and the view's
+ *   cutoff does not bound it.  The pixel's own geom is an occluder like any other (a height field or a torus shadows itself).
+ *   Consequences: a surface seen from the side the light is not on (n . l^ <= 0) gets that light's ambient term only; a camera inside
+ *   a closed geom sees the inward normal, and every light outside the geom is blocked by it.
+ * Launches in mode 1 with an active light and a colour image asked for: the depth launch, unchanged; the shade launch, which writes
+ * the normal (into engine-owned scratch if the caller takes none) and no colour; the light kernel on the same stream.
+ * The lights are read from the model once, at the engine's first such call; mjh_set_light_active(engine, light, on) switches a light
+ * for every env of the engine from the next call on (a bad id: MJH_ERR_ARG).
+ * mjh_light_options: shadows 0 casts no shadow ray; cull 0 visits every geom (1: occluders are culled per tile; the bits are the same
+ * either way); bias in metres, > 0 and finite.  A shadows or cull value other than 0 / 1, a bad bias or a NULL pointer: MJH_ERR_ARG and
+ * nothing changes.  Defaults 1, 1, 1e-3.
+ * Not modelled: textures, specular and attenuation terms, soft shadows, per-env light poses in the body frame or colours, moving light
+ * modes, lights for mjh_ray. */
+typedef struct mjh_light_options { int shadows; int cull; float bias; } mjh_light_options;
+void mjh_light_default_options(mjh_light_options*);
+int mjh_render_set_lighting(mjh_engine*, int mode);
+int mjh_render_get_lighting(const mjh_engine*);
+int mjh_render_set_light_options(mjh_engine*, const mjh_light_options*);
+int mjh_render_get_light_options(const mjh_engine*, mjh_light_options*);
+int mjh_set_light_active(mjh_engine*, int light, int on);
 
 /* zero-copy export for the single ROS state topic: packs time(1)+qpos(nq)+qvel(nv)
  * fp32 per env into a caller-provided DEVICE buffer [nenv*(1+nq+nv)] on the engine's

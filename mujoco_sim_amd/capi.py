@@ -87,6 +87,15 @@ _INT_SIZES7 = ["nmeshtri"]
 _ARRAYS7 = [("mesh_triadr", "i", "nmesh"), ("mesh_trinum", "i", "nmesh"), ("mesh_tri", "d", "9*nmeshtri")]
 # appended for colour images (behind mesh_tri)
 _ARRAYS8 = [("geom_rgba", "d", "4*ngeom")]
+# appended for lights (behind geom_rgba)
+_INT_SIZES9 = ["nlight"]
+_ARRAYS9 = [
+    ("light_bodyid", "i", "nlight"), ("light_pos", "d", "3*nlight"), ("light_dir", "d", "3*nlight"),
+    ("light_directional", "i", "nlight"), ("light_castshadow", "i", "nlight"), ("light_active", "i", "nlight"),
+    ("light_diffuse", "d", "3*nlight"), ("light_ambient", "d", "3*nlight"), ("light_cutoff", "d", "nlight"),
+    ("light_exponent", "d", "nlight"),
+]
+MAXLIGHT = 8   # MJH_MAXLIGHT
 
 
 class Model(C.Structure):
@@ -111,15 +120,18 @@ class Model(C.Structure):
         + [(n, C.c_int) for n in _INT_SIZES7]
         + [(n, c_int_p if t == "i" else c_double_p) for n, t, _ in _ARRAYS7]
         + [(n, c_int_p if t == "i" else c_double_p) for n, t, _ in _ARRAYS8]
+        + [(n, C.c_int) for n in _INT_SIZES9]
+        + [(n, c_int_p if t == "i" else c_double_p) for n, t, _ in _ARRAYS9]
+        + [("light_names", C.POINTER(C.c_char_p))]
     )
 
     def array(self, name):
         """numpy copy of a model array."""
         import numpy as np
 
-        for n, t, expr in _ARRAYS + _ARRAYS2 + _ARRAYS3 + _ARRAYS4 + _ARRAYS5 + _ARRAYS6 + _ARRAYS7 + _ARRAYS8:
+        for n, t, expr in _ARRAYS + _ARRAYS2 + _ARRAYS3 + _ARRAYS4 + _ARRAYS5 + _ARRAYS6 + _ARRAYS7 + _ARRAYS8 + _ARRAYS9:
             if n == name:
-                ln = eval(expr, {}, {k: getattr(self, k) for k in _INT_SIZES + _INT_SIZES2 + _INT_SIZES4 + _INT_SIZES5 + _INT_SIZES6 + _INT_SIZES7})
+                ln = eval(expr, {}, {k: getattr(self, k) for k in _INT_SIZES + _INT_SIZES2 + _INT_SIZES4 + _INT_SIZES5 + _INT_SIZES6 + _INT_SIZES7 + _INT_SIZES9})
                 ptr = getattr(self, n)
                 if ln == 0 or not ptr:
                     return np.zeros(0, dtype=np.int32 if t == "i" else np.float64)
@@ -140,6 +152,9 @@ class RayOptions(C.Structure):
 class DepthOptions(C.Structure):
     _fields_ = [("camera", C.c_int), ("width", C.c_int), ("height", C.c_int), ("bodyexclude", C.c_int), ("flg_static", C.c_int),
                 ("range", C.c_int), ("cull", C.c_int), ("cutoff", C.c_double)]
+
+class LightOptions(C.Structure):
+    _fields_ = [("shadows", C.c_int), ("cull", C.c_int), ("bias", C.c_float)]
 
 class RenderOptions(C.Structure):
     _fields_ = [("view", DepthOptions), ("ambient", C.c_float), ("diffuse", C.c_float), ("background", C.c_float * 4)]
@@ -176,6 +191,9 @@ SYMBOLS = [
     ("mjh_builder_add_site", C.c_int, [_vp, C.c_char_p, C.c_int, c_double_p, c_double_p]),
     ("mjh_builder_add_camera", C.c_int, [_vp, C.c_char_p, C.c_int, c_double_p, c_double_p, C.c_double]),
     ("mjh_builder_set_geom_rgba", C.c_int, [_vp, C.c_int, c_double_p]),
+    ("mjh_builder_add_light", C.c_int, [_vp, C.c_char_p, C.c_int, c_double_p, c_double_p, C.c_int, C.c_int, c_double_p, c_double_p,
+                                       C.c_double, C.c_double]),
+    ("mjh_builder_set_light_active", C.c_int, [_vp, C.c_int, C.c_int]),
     ("mjh_builder_add_sensor", C.c_int, [_vp, C.c_char_p, C.c_int, C.c_int]),
     ("mjh_builder_compile", Model_p, [_vp]),
     ("mjh_model_destroy", None, [Model_p]),
@@ -250,6 +268,12 @@ SYMBOLS = [
     ("mjh_render_default_options", None, [C.POINTER(RenderOptions)]),
     ("mjh_render", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(RenderOptions), _vp, _vp, _vp, _vp]),
     ("mjh_render_device", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(RenderOptions), _vp, _vp, _vp, _vp]),
+    ("mjh_light_default_options", None, [C.POINTER(LightOptions)]),
+    ("mjh_render_set_lighting", C.c_int, [_vp, C.c_int]),
+    ("mjh_render_get_lighting", C.c_int, [_vp]),
+    ("mjh_render_set_light_options", C.c_int, [_vp, C.POINTER(LightOptions)]),
+    ("mjh_render_get_light_options", C.c_int, [_vp, C.POINTER(LightOptions)]),
+    ("mjh_set_light_active", C.c_int, [_vp, C.c_int, C.c_int]),
     ("mjh_export_state_device", C.c_int, [_vp, _vp]),
     ("mjh_state_stride", C.c_int, [_vp]),
     ("mjh_mirror_create", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(_vp)]),

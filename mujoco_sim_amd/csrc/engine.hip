@@ -18,6 +18,7 @@
 #include "dev_ray.h"
 #include "dev_depth.h"
 #include "dev_render.h"
+#include "dev_light.h"
 #include "ray_tables.h"
 
 void mjh_set_error(const std::string& s);  // model_builder.cpp
@@ -128,6 +129,10 @@ struct mjh_engine {
   // colour images (mjh_render / mjh_render_device, render.hip): geom_rgba as float4 per geom, uploaded at the first render call; the depth
   // and geom-id images of a device-form call whose caller takes neither
   float4* ray_color = nullptr; float* render_io = nullptr; size_t render_io_floats = 0;
+  // lights (mjh_render_set_lighting, light.hip): the mode, the options, and the model's lights as the kernel takes them, read from the
+  // model once (light_tables); the active mask is applied when a call packs its launch descriptor
+  int light_mode = 0; mjh_light_options light_opt = {1, 1, 1e-3f};
+  bool lights_ready = false; int nlight = 0; LightRec lights[MJH_MAXLIGHT]; int light_on[MJH_MAXLIGHT];
 };
 
 static int pad32(int n) { return ((n + 31) / 32) * 32; }
@@ -2164,6 +2169,53 @@ static int render_tables(mjh_engine* e) {
   e->ray_color = d;
   return MJH_OK;
 }
+// ---- lights (include/mjhip.h: mjh_render_set_lighting).  The model's lights as kernel records, once per engine.
+static void light_tables(mjh_engine* e) {
+  if (e->lights_ready) return;
+  const mjh_model* m = e->model;
+  e->nlight = std::min(std::max(m->nlight, 0), MJH_MAXLIGHT);
+  for (int l = 0; l < e->nlight; l++) {
+    LightRec& R = e->lights[l];
+    R.body = m->light_bodyid[l];
+    R.flags = (m->light_directional[l] ? LIGHT_DIRECTIONAL : 0) | (m->light_castshadow[l] ? LIGHT_CASTSHADOW : 0);
+    for (int k = 0; k < 3; k++) {
+      R.pos[k] = (float)m->light_pos[3*l + k]; R.dir[k] = (float)m->light_dir[3*l + k];
+      R.dif[k] = (float)m->light_diffuse[3*l + k]; R.amb[k] = (float)m->light_ambient[3*l + k];
+    }
+    R.coscut = (float)std::cos(m->light_cutoff[l] * 3.14159265358979323846 / 180.0); R.exponent = (float)m->light_exponent[l];
+    e->light_on[l] = m->light_active[l] ? 1 : 0;
+  }
+  e->lights_ready = true;
+}
+extern "C" void mjh_light_default_options(mjh_light_options* o) { if (o) { o->shadows = 1; o->cull = 1; o->bias = 1e-3f; } }
+extern "C" int mjh_render_set_lighting(mjh_engine* e, int mode) {
+  ENG_NOJOIN(e);
+  if (mode != 0 && mode != 1) { mjh_set_error("mjh_render_set_lighting: mode must be 0 or 1"); return MJH_ERR_ARG; }
+  e->light_mode = mode;
+  return MJH_OK;
+}
+extern "C" int mjh_render_get_lighting(const mjh_engine* e) { return e ? e->light_mode : 0; }
+extern "C" int mjh_render_set_light_options(mjh_engine* e, const mjh_light_options* o) {
+  ENG_NOJOIN(e);
+  if (!o) { mjh_set_error("mjh_render_set_light_options: null pointer"); return MJH_ERR_ARG; }
+  if ((o->shadows != 0 && o->shadows != 1) || (o->cull != 0 && o->cull != 1)) { mjh_set_error("mjh_render_set_light_options: shadows and cull must be 0 or 1"); return MJH_ERR_ARG; }
+  if (!(o->bias > 0.0f && std::isfinite(o->bias))) { mjh_set_error("mjh_render_set_light_options: bias must be positive and finite"); return MJH_ERR_ARG; }
+  e->light_opt = *o;
+  return MJH_OK;
+}
+extern "C" int mjh_render_get_light_options(const mjh_engine* e, mjh_light_options* o) {
+  if (!e || !o) { mjh_set_error("mjh_render_get_light_options: null pointer"); return MJH_ERR_ARG; }
+  *o = e->light_opt;
+  return MJH_OK;
+}
+extern "C" int mjh_set_light_active(mjh_engine* e, int light, int on) {
+  ENG_NOJOIN(e);
+  light_tables(e);
+  if (light < 0 || light >= e->nlight) { mjh_set_error("mjh_set_light_active: light id out of range"); return MJH_ERR_ARG; }
+  e->light_on[light] = on ? 1 : 0;
+  return MJH_OK;
+}
+
 extern "C" int mjh_render_device(mjh_engine* e, int env0, int n, const mjh_render_options* opt, float* d_depth, int* d_geomid, float* d_normal, unsigned char* d_rgba) {
   ENG(e);
   mjh_render_options o; mjh_render_default_options(&o);
@@ -2173,21 +2225,35 @@ extern "C" int mjh_render_device(mjh_engine* e, int env0, int n, const mjh_rende
   if (!d_normal && !d_rgba) return mjh_depth_device(e, env0, n, &o.view, d_depth, d_geomid);
   rc = render_tables(e);
   if (rc) return rc;
+  // lighting mode 1 with a colour image and an active light: the shade launch writes the normal only, the light kernel the colour
+  LightArgs LA{};
+  if (e->light_mode == 1 && d_rgba) {
+    light_tables(e);
+    for (int l = 0; l < e->nlight; l++) if (e->light_on[l]) LA.L[LA.nlight++] = e->lights[l];
+  }
+  const bool lit = LA.nlight > 0;
   const size_t nout = (size_t)n * o.view.width * o.view.height;
-  if (!d_depth || !d_geomid) {
-    rc = io_reserve(e, &e->render_io, &e->render_io_floats, 2 * nout);
+  if (!d_depth || !d_geomid || (lit && !d_normal)) {
+    rc = io_reserve(e, &e->render_io, &e->render_io_floats, (lit && !d_normal ? 5 : 2) * nout);
     if (rc) return rc;
     if (!d_depth) d_depth = e->render_io;
     if (!d_geomid) d_geomid = (int*)(e->render_io + nout);
+    if (lit && !d_normal) d_normal = e->render_io + 2 * nout;
   }
   ShadeArgs A{};
   rc = depth_chain(e, env0, n, o.view, d_depth, d_geomid, &A.D);
   if (rc) return rc;
   HIPCHK(mjh_launch_depth(e->stream, A.D));
-  A.color = e->ray_color; A.normal = d_normal; A.rgba = (unsigned*)d_rgba;
+  A.color = e->ray_color; A.normal = d_normal; A.rgba = lit ? nullptr : (unsigned*)d_rgba;
   A.ambient = o.ambient; A.diffuse = o.diffuse;
   A.background = render_pack(o.background[0], o.background[1], o.background[2], o.background[3]);
   HIPCHK(mjh_launch_shade(e->stream, A));
+  if (lit) {
+    LA.D = A.D; LA.color = e->ray_color; LA.normal = d_normal; LA.rgba = (unsigned*)d_rgba;
+    LA.ambient = o.ambient; LA.diffuse = o.diffuse; LA.background = A.background;
+    LA.shadows = e->light_opt.shadows; LA.cull = e->light_opt.cull; LA.bias = e->light_opt.bias;
+    HIPCHK(mjh_launch_light(e->stream, LA));
+  }
   return MJH_OK;
 }
 extern "C" int mjh_render(mjh_engine* e, int env0, int n, const mjh_render_options* opt, float* depth, int* geomid, float* normal, unsigned char* rgba) {
@@ -2202,7 +2268,8 @@ extern "C" int mjh_render(mjh_engine* e, int env0, int n, const mjh_render_optio
   if (rc) return rc;
   float* const d_depth = e->ray_io; int* const d_gid = (int*)(e->ray_io + nout); float* const d_normal = e->ray_io + 2 * nout;
   unsigned char* const d_rgba = (unsigned char*)(e->ray_io + 5 * nout);
-  rc = mjh_render_device(e, env0, n, &o, d_depth, d_gid, normal ? d_normal : nullptr, rgba ? d_rgba : nullptr);
+  // (lighting mode 1: the light kernel reads the normal image; the staging buffer has room for it whether or not the caller takes it)
+  rc = mjh_render_device(e, env0, n, &o, d_depth, d_gid, (normal || (rgba && e->light_mode == 1)) ? d_normal : nullptr, rgba ? d_rgba : nullptr);
   if (rc) return rc;
   if (depth) HIPCHK(hipMemcpyAsync(depth, d_depth, nout * sizeof(float), hipMemcpyDeviceToHost, e->stream));
   if (geomid) HIPCHK(hipMemcpyAsync(geomid, d_gid, nout * sizeof(int), hipMemcpyDeviceToHost, e->stream));

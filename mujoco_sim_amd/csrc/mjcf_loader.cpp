@@ -3,7 +3,7 @@
 // the step path: <compiler angle autolimits>, <option timestep gravity impratio iterations tolerance>,
 // root <default> (<geom>, <joint>), <worldbody>/<body> trees with <inertial>, <joint> (free, ball, hinge, slide),
 // <freejoint>, <geom> (plane, sphere, capsule, cylinder, box, ellipsoid, mesh: binary / ASCII STL and OBJ assets become convex hulls), gravcomp,
-// <contact><exclude>, <equality><joint polycoef> / <weld> / <connect>, <body mocap>, <site>, <camera> (fixed mode; quat | euler | xyaxes, fovy), <sensor><force> / <torque>.  Everything is translated into mjh_builder_* calls; physics
+// <contact><exclude>, <equality><joint polycoef> / <weld> / <connect>, <body mocap>, <site>, <camera> (fixed mode; quat | euler | xyaxes, fovy), <light> (fixed mode; no specular, no attenuation), <sensor><force> / <torque>.  Everything is translated into mjh_builder_* calls; physics
 // defaults follow MuJoCo's documented defaults (angle = degree, hinge axis 0 0 1, geom type sphere, ...).
 // <asset><hfield> (inline elevation or MuJoCo's binary file; PNG files are skipped with their geoms) and hfield geoms on static bodies.
 // Not handled (reported in the returned note, mjh_load_note): tendons, actuators, PNG height fields, sensors other than force / torque.
@@ -153,6 +153,7 @@ struct Loader {
   std::string note, basedir, meshdir;   // directory of the file being read (empty for a string), <compiler meshdir>
   int nameless = 0;
   int ncamera = 0;      // cameras loaded so far: a nameless one is camera<id>
+  int nlight = 0;       // lights loaded so far: a nameless one is light<id>
 
   double ang(double v) const { return degree ? v * 3.14159265358979323846 / 180.0 : v; }
   bool orientation(const Node& n, double* quat) {   // quat | euler (xyz) ; returns false if neither
@@ -343,7 +344,23 @@ struct Loader {
         }
         if (mjh_builder_add_camera(b, name.c_str(), body, pos, quat, fovy) < 0) return false;
         ncamera++;
-      } else if (c->tag != "light") note += "ignored <" + c->tag + ">; ";
+      } else if (c->tag == "light") {
+        // fixed lights only (an absent mode is "fixed"); specular and attenuation are not modelled
+        const Node l = with_defaults(*c);
+        std::string name = l.get("name") ? l.get("name") : ("light" + std::to_string(nlight));
+        if (l.get("mode") && std::string(l.get("mode")) != "fixed") { note += "skipped <light " + name + " mode=\"" + l.get("mode") + "\"> (only fixed lights are loaded); "; continue; }
+        if (nlight >= MJH_MAXLIGHT) { note += "skipped <light " + name + "> (a model holds at most " + std::to_string(MJH_MAXLIGHT) + " lights); "; continue; }
+        double pos[3] = {0, 0, 0}, dir[3] = {0, 0, -1}, dif[3] = {0.7, 0.7, 0.7}, amb[3] = {0, 0, 0}, cutoff = 45, exponent = 10, att[3] = {1, 0, 0};
+        nums(l.get("pos"), pos, 3); nums(l.get("dir"), dir, 3); nums(l.get("diffuse"), dif, 3); nums(l.get("ambient"), amb, 3);
+        nums(l.get("cutoff"), &cutoff, 1); nums(l.get("exponent"), &exponent, 1);
+        auto flag = [&](const char* a, bool dflt) { const char* v = l.get(a); return v ? std::string(v) == "true" : dflt; };
+        const bool unmodelled = l.get("specular") || (nums(l.get("attenuation"), att, 3) > 0 && (att[0] != 1 || att[1] != 0 || att[2] != 0));
+        if (unmodelled) note += "ignored specular / attenuation of <light " + name + "> (not modelled); ";
+        const int id = mjh_builder_add_light(b, name.c_str(), body, pos, dir, flag("directional", false), flag("castshadow", true), dif, amb, cutoff, exponent);
+        if (id < 0) return false;
+        if (!flag("active", true)) mjh_builder_set_light_active(b, id, 0);
+        nlight++;
+      } else note += "ignored <" + c->tag + ">; ";
     }
     return true;
   }

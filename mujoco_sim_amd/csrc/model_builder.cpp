@@ -50,6 +50,7 @@ struct BEq { int type = MJH_EQ_JOINT; int j1 = -1, j2 = -1; double poly[5] = {0,
 struct BSite { std::string name; int body; double pos[3], quat[4]; };
 struct BSensor { std::string name; int type, site; };
 struct BCamera { std::string name; int body; double pos[3], quat[4], fovy; };
+struct BLight { std::string name; int body, directional, castshadow, active; double pos[3], dir[3], diffuse[3], ambient[3], cutoff, exponent; };
 
 }  // namespace
 
@@ -68,6 +69,7 @@ struct mjh_builder {
   std::vector<BSite> sites;
   std::vector<BSensor> sensors;
   std::vector<BCamera> cameras;
+  std::vector<BLight> lights;
   std::vector<int> mocap;       // builder body ids flagged <body mocap="true">
 };
 
@@ -579,6 +581,27 @@ extern "C" int mjh_builder_add_camera(mjh_builder* b, const char* name, int body
   for (int i = 0; i < 3; i++) x.pos[i] = pos ? pos[i] : 0;
   if (quat) { for (int i = 0; i < 4; i++) x.quat[i] = quat[i]; hm::normalize4(x.quat); } else { x.quat[0] = 1; x.quat[1] = x.quat[2] = x.quat[3] = 0; }
   b->cameras.push_back(x); return (int)b->cameras.size() - 1;
+}
+extern "C" int mjh_builder_add_light(mjh_builder* b, const char* name, int body, const double pos[3], const double dir[3], int directional,
+                                     int castshadow, const double diffuse[3], const double ambient[3], double cutoff_deg, double exponent) {
+  if (!b || body < 0 || body >= (int)b->bodies.size()) { g_err = "add_light: bad body"; return MJH_ERR_ARG; }
+  if ((int)b->lights.size() >= MJH_MAXLIGHT) { g_err = "add_light: a model holds at most MJH_MAXLIGHT (8) lights"; return MJH_ERR_ARG; }
+  BLight x; x.name = name ? name : ""; x.body = body; x.active = 1;
+  x.directional = directional < 0 ? 0 : (directional ? 1 : 0); x.castshadow = castshadow < 0 ? 1 : (castshadow ? 1 : 0);
+  // [UPSTREAM, unverified here] MuJoCo's light defaults: pos 0 0 0, dir 0 0 -1, diffuse 0.7 0.7 0.7, ambient 0 0 0
+  for (int i = 0; i < 3; i++) { x.pos[i] = pos ? pos[i] : 0.0; x.dir[i] = dir ? dir[i] : (i == 2 ? -1.0 : 0.0); x.diffuse[i] = diffuse ? diffuse[i] : 0.7; x.ambient[i] = ambient ? ambient[i] : 0.0; }
+  for (int i = 0; i < 3; i++) if (!std::isfinite(x.pos[i]) || !std::isfinite(x.dir[i])) { g_err = "add_light: pos and dir must be finite"; return MJH_ERR_ARG; }
+  if (!(hm::normalize3(x.dir) > 1e-12)) { g_err = "add_light: dir is zero"; return MJH_ERR_ARG; }
+  for (int i = 0; i < 3; i++) if (!(x.diffuse[i] >= 0.0 && std::isfinite(x.diffuse[i]) && x.ambient[i] >= 0.0 && std::isfinite(x.ambient[i]))) { g_err = "add_light: colour components must be finite and not negative"; return MJH_ERR_ARG; }
+  if (!(cutoff_deg > 0.0 && cutoff_deg <= 180.0)) { g_err = "add_light: cutoff must lie in (0, 180] degrees"; return MJH_ERR_ARG; }
+  if (!(exponent >= 0.0 && std::isfinite(exponent))) { g_err = "add_light: exponent must be finite and not negative"; return MJH_ERR_ARG; }
+  x.cutoff = cutoff_deg; x.exponent = exponent;
+  b->lights.push_back(x); return (int)b->lights.size() - 1;
+}
+extern "C" int mjh_builder_set_light_active(mjh_builder* b, int light, int on) {
+  if (!b || light < 0 || light >= (int)b->lights.size()) { g_err = "set_light_active: bad light"; return MJH_ERR_ARG; }
+  b->lights[light].active = on ? 1 : 0;
+  return MJH_OK;
 }
 extern "C" int mjh_builder_set_geom_rgba(mjh_builder* b, int geom, const double rgba[4]) {
   if (!b || geom < 0 || geom >= (int)b->geoms.size() || !rgba) { g_err = "set_geom_rgba: bad geom"; return MJH_ERR_ARG; }
@@ -1188,6 +1211,22 @@ extern "C" mjh_model* mjh_builder_compile(mjh_builder* B) {
     m->cam_bodyid = dup(cam_bodyid); m->cam_pos = dup(cam_pos); m->cam_quat = dup(cam_quat); m->cam_fovy = dup(cam_fovy);
     m->cam_names = dupnames(cam_names);
   }
+  {   // lights: frame in the body, body ids renumbered as the cameras' are
+    const int nl = (int)B->lights.size();
+    std::vector<int> bodyid(nl), directional(nl), castshadow(nl), active(nl);
+    std::vector<double> pos(3*nl), dir(3*nl), diffuse(3*nl), ambient(3*nl), cutoff(nl), exponent(nl); std::vector<std::string> names(nl);
+    for (int i = 0; i < nl; i++) {
+      const BLight& L = B->lights[i];
+      bodyid[i] = newid[L.body]; names[i] = L.name; directional[i] = L.directional; castshadow[i] = L.castshadow; active[i] = L.active;
+      cutoff[i] = L.cutoff; exponent[i] = L.exponent;
+      for (int k = 0; k < 3; k++) { pos[3*i+k] = L.pos[k]; dir[3*i+k] = L.dir[k]; diffuse[3*i+k] = L.diffuse[k]; ambient[3*i+k] = L.ambient[k]; }
+    }
+    m->nlight = nl;
+    m->light_bodyid = dup(bodyid); m->light_pos = dup(pos); m->light_dir = dup(dir);
+    m->light_directional = dup(directional); m->light_castshadow = dup(castshadow); m->light_active = dup(active);
+    m->light_diffuse = dup(diffuse); m->light_ambient = dup(ambient); m->light_cutoff = dup(cutoff); m->light_exponent = dup(exponent);
+    m->light_names = dupnames(names);
+  }
   return m;
 }
 
@@ -1197,6 +1236,7 @@ extern "C" mjh_model* mjh_model_replicate(const mjh_model* a, int G) {
   if (a->nsite || a->nsensor || a->nmocap) { g_err = "mjh_model_replicate: models with sites, sensors or mocap bodies are not packed"; return nullptr; }
   if (a->nhfield > 0) { g_err = "mjh_model_replicate: models with height fields are not packed"; return nullptr; }
   if (a->ncam > 0) { g_err = "mjh_model_replicate: models with cameras are not packed"; return nullptr; }
+  if (a->nlight > 0) { g_err = "mjh_model_replicate: models with lights are not packed"; return nullptr; }
   for (int e = 0; e < a->neq; e++) if (a->eq_type[e] != MJH_EQ_JOINT) { g_err = "mjh_model_replicate: connect / weld equalities are not packed"; return nullptr; }
   const int nb = a->nbody, nj = a->njnt, nv = a->nv, nq = a->nq, ng = a->ngeom, nt = a->ntree, ne = a->neq, np = a->npair, nM = a->nM;
   std::vector<int> moving_b, moving_g;
@@ -1334,27 +1374,29 @@ extern "C" void mjh_model_destroy(mjh_model* m) {
     m->site_bodyid, m->site_pos, m->site_quat, m->sensor_type, m->sensor_objid, m->sensor_adr, m->body_mocapid,
     m->hfield_nrow, m->hfield_ncol, m->hfield_adr, m->hfield_size, m->hfield_data,
     m->mesh_planeadr, m->mesh_planenum, m->mesh_plane, m->cam_bodyid, m->cam_pos, m->cam_quat, m->cam_fovy,
-    m->mesh_triadr, m->mesh_trinum, m->mesh_tri, m->geom_rgba};
+    m->mesh_triadr, m->mesh_trinum, m->mesh_tri, m->geom_rgba,
+    m->light_bodyid, m->light_pos, m->light_dir, m->light_directional, m->light_castshadow, m->light_active,
+    m->light_diffuse, m->light_ambient, m->light_cutoff, m->light_exponent};
   for (void* p : ptrs) std::free(p);
   auto freen = [](char** n, int c) { if (!n) return; for (int i = 0; i < c; i++) std::free(n[i]); std::free(n); };
   freen(m->body_names, m->nbody); freen(m->jnt_names, m->njnt); freen(m->geom_names, m->ngeom);
   freen(m->site_names, m->nsite); freen(m->sensor_names, m->nsensor); freen(m->hfield_names, m->nhfield);
-  freen(m->cam_names, m->ncam);
+  freen(m->cam_names, m->ncam); freen(m->light_names, m->nlight);
   std::free(m);
 }
 
 extern "C" int mjh_name2id(const mjh_model* m, int objtype, const char* name) {
   if (!m || !name) return -1;
-  char** t = objtype == 0 ? m->body_names : objtype == 1 ? m->jnt_names : objtype == 2 ? m->geom_names : objtype == 3 ? m->site_names : objtype == 5 ? m->cam_names : m->sensor_names;
-  int n = objtype == 0 ? m->nbody : objtype == 1 ? m->njnt : objtype == 2 ? m->ngeom : objtype == 3 ? m->nsite : objtype == 5 ? m->ncam : m->nsensor;
-  if (!t || objtype < 0 || objtype > 5) return -1;     // a model assembled without name tables
+  char** t = objtype == 0 ? m->body_names : objtype == 1 ? m->jnt_names : objtype == 2 ? m->geom_names : objtype == 3 ? m->site_names : objtype == 5 ? m->cam_names : objtype == 6 ? m->light_names : m->sensor_names;
+  int n = objtype == 0 ? m->nbody : objtype == 1 ? m->njnt : objtype == 2 ? m->ngeom : objtype == 3 ? m->nsite : objtype == 5 ? m->ncam : objtype == 6 ? m->nlight : m->nsensor;
+  if (!t || objtype < 0 || objtype > 6) return -1;     // a model assembled without name tables
   for (int i = 0; i < n; i++) if (t[i] && std::strcmp(t[i], name) == 0) return i;
   return -1;
 }
 extern "C" const char* mjh_id2name(const mjh_model* m, int objtype, int id) {
   if (!m) return nullptr;
-  char** t = objtype == 0 ? m->body_names : objtype == 1 ? m->jnt_names : objtype == 2 ? m->geom_names : objtype == 3 ? m->site_names : objtype == 5 ? m->cam_names : m->sensor_names;
-  int n = objtype == 0 ? m->nbody : objtype == 1 ? m->njnt : objtype == 2 ? m->ngeom : objtype == 3 ? m->nsite : objtype == 5 ? m->ncam : m->nsensor;
-  if (!t || objtype < 0 || objtype > 5 || id < 0 || id >= n) return nullptr;
+  char** t = objtype == 0 ? m->body_names : objtype == 1 ? m->jnt_names : objtype == 2 ? m->geom_names : objtype == 3 ? m->site_names : objtype == 5 ? m->cam_names : objtype == 6 ? m->light_names : m->sensor_names;
+  int n = objtype == 0 ? m->nbody : objtype == 1 ? m->njnt : objtype == 2 ? m->ngeom : objtype == 3 ? m->nsite : objtype == 5 ? m->ncam : objtype == 6 ? m->nlight : m->nsensor;
+  if (!t || objtype < 0 || objtype > 6 || id < 0 || id >= n) return nullptr;
   return t[id];
 }

@@ -31,7 +31,7 @@ class Model:
 
     def __getattr__(self, name):
         c = self.__dict__.get("c")
-        if c is not None and name in capi._INT_SIZES + capi._INT_SIZES2 + capi._INT_SIZES4 + capi._INT_SIZES6 + capi._INT_SIZES7 + ["meaninertia", "opt"]:
+        if c is not None and name in capi._INT_SIZES + capi._INT_SIZES2 + capi._INT_SIZES4 + capi._INT_SIZES6 + capi._INT_SIZES7 + capi._INT_SIZES9 + ["meaninertia", "opt"]:
             return getattr(c, name)
         raise AttributeError(name)
 
@@ -434,6 +434,41 @@ class Engine:
         o = self._render_options(camera, width, height, dict(options))
         _chk(self.lib, self.lib.mjh_render_device(self.h, env0, n, C.byref(o), C.c_void_p(d_depth), C.c_void_p(d_geomid),
                                                   C.c_void_p(d_normal), C.c_void_p(d_rgba)), "mjh_render_device")
+
+    # ---- lights and cast shadows in the colour image
+    @property
+    def render_lighting(self):
+        """0: the colour image is shaded by the headlight alone (the default); 1: it also takes the model's active lights
+        (mjh_render_set_lighting)"""
+        return self.lib.mjh_render_get_lighting(self.h)
+
+    @render_lighting.setter
+    def render_lighting(self, mode):
+        _chk(self.lib, self.lib.mjh_render_set_lighting(self.h, int(mode)), "mjh_render_set_lighting")
+
+    @property
+    def light_options(self):
+        """dict(shadows, cull, bias) of mjh_light_options; assign a dict with any of the three keys"""
+        o = capi.LightOptions()
+        _chk(self.lib, self.lib.mjh_render_get_light_options(self.h, C.byref(o)), "mjh_render_get_light_options")
+        return {"shadows": o.shadows, "cull": o.cull, "bias": o.bias}
+
+    @light_options.setter
+    def light_options(self, options):
+        cur = self.light_options
+        for k in options:
+            if k not in cur:
+                raise TypeError(f"unknown light option {k!r}")
+        cur.update(options)
+        o = capi.LightOptions(int(cur["shadows"]), int(cur["cull"]), float(cur["bias"]))
+        _chk(self.lib, self.lib.mjh_render_set_light_options(self.h, C.byref(o)), "mjh_render_set_light_options")
+
+    def set_light_active(self, light, on):
+        """switch light `light` (id or name) for every env of the engine, from the next render call on"""
+        if isinstance(light, (str, bytes)):
+            name = light.encode() if isinstance(light, str) else light
+            light = self.lib.mjh_name2id(self.lib.mjh_engine_model(self.h), 6, name)
+        _chk(self.lib, self.lib.mjh_set_light_active(self.h, int(light), int(bool(on))), "mjh_set_light_active")
 
     def export_state_device(self, device_ptr):
         _chk(self.lib, self.lib.mjh_export_state_device(self.h, C.c_void_p(device_ptr)), "mjh_export_state_device")

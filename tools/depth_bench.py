@@ -55,8 +55,9 @@ def add_camera(lib, b, view):
     assert cid == 0, lib.mjh_last_error()
 
 
-def s24_with_camera(lib):
-    """mjh_scene_s24 has no camera and a compiled model takes none: the same scene built again from its own tables"""
+def s24_with_camera(lib, extra=None):
+    """mjh_scene_s24 has no camera and a compiled model takes none: the same scene built again from its own tables.  extra(lib, b): further
+    builder calls before the compile step (tools/light_bench.py adds its lights)"""
     import mujoco_sim_amd as ms
     from helpers import D
     s = ms.scene("s24")
@@ -75,6 +76,8 @@ def s24_with_camera(lib):
         assert lib.mjh_builder_add_geom(b, lib.mjh_id2name(s.ptr, 2, g), ids[int(gb[g])], int(gt[g]), D(*gs[g]), D(*gp[g]), D(*gq[g]), D(*gf[g]),
                                         int(cd[g]), int(ct[g]), int(ca[g]), -1) >= 0
     add_camera(lib, b, S24_VIEW)
+    if extra:
+        extra(lib, b)
     p = lib.mjh_builder_compile(b)
     assert p, lib.mjh_last_error()
     m = ms.Model(p, lib)
@@ -84,7 +87,7 @@ def s24_with_camera(lib):
     return m, s
 
 
-def tetra_with_camera(lib):
+def tetra_with_camera(lib, extra=None):
     import mujoco_sim_amd as ms
     import ray_mesh_ref as rm
     import ray_ref as rr
@@ -102,6 +105,8 @@ def tetra_with_camera(lib):
     lib.mjh_builder_add_joint(b, None, bd, 0, None, None, None, 0, 0, 0, 0, 0)
     lib.mjh_builder_add_geom(b, b"fg", bd, rr.SPHERE, D(0.05, 0, 0), None, None, None, -1, 0, 0, -1)
     add_camera(lib, b, TETRA_VIEW)
+    if extra:
+        extra(lib, b)
     p = lib.mjh_builder_compile(b)
     assert p, lib.mjh_last_error()
     m = ms.Model(p, lib)
