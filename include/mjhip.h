@@ -201,9 +201,22 @@ typedef struct mjh_model {
   double *light_diffuse, *light_ambient;  /* [3 nlight] each: r, g, b, finite and not negative */
   double *light_cutoff, *light_exponent;  /* [nlight] each: spot cone half-angle in degrees, (0, 180]; spot exponent >= 0 */
   char** light_names;
+  /* ---- appended for textures (older fields keep their offsets) ----
+   * <texture type="2d">: texel tables, and per geom the texture its material names (materials stay flattened into the geom, as
+   * geom_rgba is).  mjh_render's colour image samples them when the engine's texturing mode is 1 (mjh_render_set_texturing below,
+   * where the mapping stands).  A model assembled from tables has ntex = 0 and NULL pointers. */
+  int ntex, ntexdata;                     /* ntexdata in texels */
+  int *tex_width, *tex_height, *tex_adr;  /* [ntex] each; tex_adr in texels */
+  unsigned char* tex_rgb;                 /* [3*ntexdata]: row-major, row 0 first, R G B per texel */
+  char** tex_names;
+  int* geom_texid;                        /* [ngeom], -1 for none */
+  double* geom_texrepeat;                 /* [2*ngeom] */
+  int* geom_texuniform;                   /* [ngeom], 0 / 1 */
 } mjh_model;
 
 #define MJH_MAXLIGHT 8   /* lights a model can hold (they travel to the light kernel in its arguments) */
+#define MJH_MAXTEXSIZE 4096        /* width and height of a texture: 1 ... MJH_MAXTEXSIZE each */
+#define MJH_MAXTEXDATA (1 << 24)   /* the texels of all textures of a model total at most this */
 
 /* ------------------------------------------------- model builder (host) */
 /* Replaces the model-ingest boundary mj_loadXML (include/mujoco_sim/mj_util.h:190)
@@ -276,6 +289,27 @@ int mjh_builder_set_geom_rgba(mjh_builder*, int geom, const double rgba[4]);
 int mjh_builder_add_light(mjh_builder*, const char* name, int body, const double pos[3], const double dir[3], int directional,
                           int castshadow, const double diffuse[3], const double ambient[3], double cutoff_deg, double exponent);
 int mjh_builder_set_light_active(mjh_builder*, int light, int on);   /* <light active>: the model's light_active (a bad id: MJH_ERR_ARG) */
+/* <texture type="2d">.  Limits: width and height 1 ... MJH_MAXTEXSIZE each, the texels of all textures of a model at most
+ * MJH_MAXTEXDATA.  Beyond them, or with a NULL pointer / a bad enum / a colour component outside [0, 1]: MJH_ERR_ARG, nothing is added.
+ * mjh_builder_add_texture takes the caller's texels (3 width height bytes, row-major, row 0 first, R G B) and returns the texture id.
+ * mjh_builder_add_texture_builtin generates them on the host; MuJoCo is on no machine this runs on, so the definitions are these
+ * [UPSTREAM, unverified here: MuJoCo's builtin textures and marks]:
+ *   a byte is (int)(255 c + 0.5) for c in [0, 1];
+ *   flat: every texel is rgb1;
+ *   checker: texel (row j, column i) is rgb1 where (j < H/2) == (i < W/2) (integer division), rgb2 elsewhere: one repetition of the
+ *     texture is 2 x 2 squares;
+ *   gradient: x = 2i/(W-1) - 1, y = 2j/(H-1) - 1 (0 where the dimension is 1), r = min(1, sqrt(x^2 + y^2)), colour rgb1 (1 - r) + rgb2 r;
+ *   mark edge: row 0, row H-1, column 0 and column W-1 take markrgb; mark cross: row H/2 and column W/2 take markrgb.
+ * NULL rgb1 / rgb2 / markrgb take 0.8 0.8 0.8 / 0.5 0.5 0.5 / 0 0 0 [UPSTREAM, unverified here: MuJoCo's texture defaults]. */
+enum mjh_texbuiltin { MJH_TEXBUILTIN_FLAT = 0, MJH_TEXBUILTIN_CHECKER = 1, MJH_TEXBUILTIN_GRADIENT = 2 };
+enum mjh_texmark { MJH_TEXMARK_NONE = 0, MJH_TEXMARK_EDGE = 1, MJH_TEXMARK_CROSS = 2 };
+int mjh_builder_add_texture(mjh_builder*, const char* name, int width, int height, const unsigned char* rgb);
+int mjh_builder_add_texture_builtin(mjh_builder*, const char* name, int builtin, int mark, int width, int height,
+                                    const double rgb1[3], const double rgb2[3], const double markrgb[3]);
+/* a material's texture, texrepeat, texuniform on geom `geom` (a builder geom id, as for mjh_builder_set_geom_rgba).  tex = -1 clears
+ * (texrepeat may then be NULL).  NULL texrepeat is 1 1; its components must be finite and > 0.  A bad geom or texture id, a bad
+ * texrepeat: MJH_ERR_ARG, nothing is changed.  A mesh geom takes no texture (its texture coordinates are not kept): MJH_ERR_ARG. */
+int mjh_builder_set_geom_texture(mjh_builder*, int geom, int tex, const double texrepeat[2], int texuniform);
 /* compile: derives inertias, qpos0, invweight0, meaninertia, rbound, pair list */
 mjh_model* mjh_builder_compile(mjh_builder*);
 void mjh_model_destroy(mjh_model*);
@@ -288,7 +322,7 @@ void mjh_model_destroy(mjh_model*);
  * continue until the slowest instance has converged), `time`, the statistics row and the bad-state reset.  Contact
  * and row capacities scale with `copies`.  Returns a new model (mjh_model_destroy) or NULL. */
 mjh_model* mjh_model_replicate(const mjh_model* m, int copies);
-int mjh_name2id(const mjh_model*, int objtype /*0 body,1 joint,2 geom,3 site,4 sensor,5 camera,6 light*/, const char* name);
+int mjh_name2id(const mjh_model*, int objtype /*0 body,1 joint,2 geom,3 site,4 sensor,5 camera,6 light,7 texture*/, const char* name);
 const char* mjh_id2name(const mjh_model*, int objtype, int id);
 
 /* MJCF-subset loader: replaces load_XML -> mj_loadXML (include/mujoco_sim/mj_util.h:185-193) for the element
@@ -317,6 +351,13 @@ mjh_model* mjh_load_mjcf_files_opt(const char* const* paths, int n, const mjh_lo
 /* 1 (default): <asset><mesh> files are read and mesh geoms collide as convex hulls; 0: mesh geoms are dropped (and
  * listed in mjh_load_note), which leaves the primitive collision geometry only */
 void mjh_load_set_mesh_mode(int mode);
+/* 0 (default): <texture> is not read and a material's texture / texrepeat / texuniform get the "ignored material attribute" note
+ * (the compiled model has ntex = 0).  1: <asset><texture type="2d" builtin="flat|checker|gradient"> becomes a texture of the model
+ * (mjh_builder_add_texture_builtin) and a material's texture, texrepeat (1 1) and texuniform (false) go to every geom that names the
+ * material, whichever colour the geom takes.  Skipped with a note, the geoms keeping their plain colour: cube and skybox textures,
+ * file textures (no image decoder), mark="random", a texture over the limits, a material that names an unknown texture, a texture
+ * on a mesh geom.  Thread-local, like the other load settings. */
+void mjh_load_set_textures(int mode);
 /* rosparam ~disable_gravity of the reference (robot.yaml:19, default true): MjSim::init_tmp rewrites gravcomp on EVERY
  * body of a robot file — 1 if set, 0 otherwise (mj_sim.cpp:301-310).  mode 1 / 0 does the same to the bodies of the files
  * after the first one in mjh_load_mjcf_files; -1 (default) keeps what the files say. */
@@ -626,7 +667,7 @@ int mjh_render(mjh_engine*, int env0, int n, const mjh_render_options*, float* d
  * mjh_light_options: shadows 0 casts no shadow ray; cull 0 visits every geom (1: occluders are culled per tile; the bits are the same
  * either way); bias in metres, > 0 and finite.  A shadows or cull value other than 0 / 1, a bad bias or a NULL pointer: MJH_ERR_ARG and
  * nothing changes.  Defaults 1, 1, 1e-3.
- * Not modelled: textures, specular and attenuation terms, soft shadows, per-env light poses in the body frame or colours, moving light
+ * Not modelled: specular and attenuation terms, soft shadows, per-env light poses in the body frame or colours, moving light
  * modes, lights for mjh_ray. */
 typedef struct mjh_light_options { int shadows; int cull; float bias; } mjh_light_options;
 void mjh_light_default_options(mjh_light_options*);
@@ -635,6 +676,25 @@ int mjh_render_get_lighting(const mjh_engine*);
 int mjh_render_set_light_options(mjh_engine*, const mjh_light_options*);
 int mjh_render_get_light_options(const mjh_engine*, mjh_light_options*);
 int mjh_set_light_active(mjh_engine*, int light, int on);
+
+/* Textures in the colour image.  mjh_render_set_texturing(engine, mode): 0 (the default) is the calls above — the same launches and the
+ * same bits whether or not the model has textures; 1: where a pixel's geom carries a texture (geom_texid >= 0) its base colour is
+ * geom_rgba[g][c] * (t_c / 255) per channel c of R, G, B, with t the texel below; the alpha stays the geom's; everything else (shade,
+ * lights, shadows, level()) is as above.  Any other mode returns MJH_ERR_ARG and changes nothing.  Depth, geom id and normal are
+ * mode 0's bits in either mode, and so is every pixel whose geom has no texture.
+ *   The texel [UPSTREAM, unverified here: MuJoCo's object-linear projection of a 2D texture along the geom's z axis]: with h the hit
+ *   point in the geom's frame, X = h_x / a_x, Y = h_y / a_y, where a = (1, 1) if geom_texuniform, else the geom's half extents in x
+ *   and y from the env's size row: plane size[0..1] (a component of 0, an infinite plane, counts as 1), box and ellipsoid
+ *   size[0..1], sphere, capsule and cylinder (r, r), height field hfield_size[0..1].  u = 0.5 rx X + 0.5, v = 0.5 - 0.5 ry Y with
+ *   (rx, ry) = geom_texrepeat; column i = min(W-1, floor((u - floor u) W)), row j the same from v and H.  Nearest texel, in fp32: no
+ *   filtering, no mip levels.  The sides of a box show the texture stretched along z.
+ * Launches in mode 1 with a colour image asked for and ntex > 0: the depth launch, unchanged; the texture kernel, which writes one
+ * word per pixel (R, G, B, flag) into engine-owned scratch; the shade launch; the light kernel (lighting mode 1 only).  The textures
+ * are uploaded once per engine, at its first such call.
+ * Not modelled: file, cube and skybox textures, mark="random", textures on mesh geoms, per-env textures, reflectance / specular /
+ * emission. */
+int mjh_render_set_texturing(mjh_engine*, int mode);
+int mjh_render_get_texturing(const mjh_engine*);
 
 /* zero-copy export for the single ROS state topic: packs time(1)+qpos(nq)+qvel(nv)
  * fp32 per env into a caller-provided DEVICE buffer [nenv*(1+nq+nv)] on the engine's

@@ -96,6 +96,15 @@ _ARRAYS9 = [
     ("light_exponent", "d", "nlight"),
 ]
 MAXLIGHT = 8   # MJH_MAXLIGHT
+# appended for textures (behind light_names); "B": unsigned char
+_INT_SIZES10 = ["ntex", "ntexdata"]
+_ARRAYS10 = [("tex_width", "i", "ntex"), ("tex_height", "i", "ntex"), ("tex_adr", "i", "ntex"), ("tex_rgb", "B", "3*ntexdata")]
+_ARRAYS10B = [("geom_texid", "i", "ngeom"), ("geom_texrepeat", "d", "2*ngeom"), ("geom_texuniform", "i", "ngeom")]
+c_ubyte_p = C.POINTER(C.c_ubyte)
+_PTR = {"i": c_int_p, "d": c_double_p, "B": c_ubyte_p}
+MAXTEXSIZE, MAXTEXDATA = 4096, 1 << 24   # MJH_MAXTEXSIZE, MJH_MAXTEXDATA
+TEXBUILTIN = {"flat": 0, "checker": 1, "gradient": 2}   # enum mjh_texbuiltin
+TEXMARK = {"none": 0, "edge": 1, "cross": 2}            # enum mjh_texmark
 
 
 class Model(C.Structure):
@@ -123,18 +132,22 @@ class Model(C.Structure):
         + [(n, C.c_int) for n in _INT_SIZES9]
         + [(n, c_int_p if t == "i" else c_double_p) for n, t, _ in _ARRAYS9]
         + [("light_names", C.POINTER(C.c_char_p))]
+        + [(n, C.c_int) for n in _INT_SIZES10]
+        + [(n, _PTR[t]) for n, t, _ in _ARRAYS10]
+        + [("tex_names", C.POINTER(C.c_char_p))]
+        + [(n, _PTR[t]) for n, t, _ in _ARRAYS10B]
     )
 
     def array(self, name):
         """numpy copy of a model array."""
         import numpy as np
 
-        for n, t, expr in _ARRAYS + _ARRAYS2 + _ARRAYS3 + _ARRAYS4 + _ARRAYS5 + _ARRAYS6 + _ARRAYS7 + _ARRAYS8 + _ARRAYS9:
+        for n, t, expr in _ARRAYS + _ARRAYS2 + _ARRAYS3 + _ARRAYS4 + _ARRAYS5 + _ARRAYS6 + _ARRAYS7 + _ARRAYS8 + _ARRAYS9 + _ARRAYS10 + _ARRAYS10B:
             if n == name:
-                ln = eval(expr, {}, {k: getattr(self, k) for k in _INT_SIZES + _INT_SIZES2 + _INT_SIZES4 + _INT_SIZES5 + _INT_SIZES6 + _INT_SIZES7 + _INT_SIZES9})
+                ln = eval(expr, {}, {k: getattr(self, k) for k in _INT_SIZES + _INT_SIZES2 + _INT_SIZES4 + _INT_SIZES5 + _INT_SIZES6 + _INT_SIZES7 + _INT_SIZES9 + _INT_SIZES10})
                 ptr = getattr(self, n)
                 if ln == 0 or not ptr:
-                    return np.zeros(0, dtype=np.int32 if t == "i" else np.float64)
+                    return np.zeros(0, dtype={"i": np.int32, "d": np.float64, "B": np.uint8}[t])
                 return np.ctypeslib.as_array(ptr, shape=(ln,)).copy()
         raise KeyError(name)
 
@@ -194,6 +207,9 @@ SYMBOLS = [
     ("mjh_builder_add_light", C.c_int, [_vp, C.c_char_p, C.c_int, c_double_p, c_double_p, C.c_int, C.c_int, c_double_p, c_double_p,
                                        C.c_double, C.c_double]),
     ("mjh_builder_set_light_active", C.c_int, [_vp, C.c_int, C.c_int]),
+    ("mjh_builder_add_texture", C.c_int, [_vp, C.c_char_p, C.c_int, C.c_int, c_ubyte_p]),
+    ("mjh_builder_add_texture_builtin", C.c_int, [_vp, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p]),
+    ("mjh_builder_set_geom_texture", C.c_int, [_vp, C.c_int, C.c_int, c_double_p, C.c_int]),
     ("mjh_builder_add_sensor", C.c_int, [_vp, C.c_char_p, C.c_int, C.c_int]),
     ("mjh_builder_compile", Model_p, [_vp]),
     ("mjh_model_destroy", None, [Model_p]),
@@ -208,6 +224,7 @@ SYMBOLS = [
     ("mjh_load_mjcf_files_opt", Model_p, [C.POINTER(C.c_char_p), C.c_int, C.POINTER(LoadOptions)]),
     ("mjh_load_set_bounds", None, [C.c_double, C.c_double]),
     ("mjh_load_set_mesh_mode", None, [C.c_int]),
+    ("mjh_load_set_textures", None, [C.c_int]),
     ("mjh_load_set_robot_gravcomp", None, [C.c_int]),
     ("mjh_load_set_odom_joints", None, [C.c_uint]),
     ("mjh_load_set_parent_child_exclude", None, [C.c_int]),
@@ -274,6 +291,8 @@ SYMBOLS = [
     ("mjh_render_set_light_options", C.c_int, [_vp, C.POINTER(LightOptions)]),
     ("mjh_render_get_light_options", C.c_int, [_vp, C.POINTER(LightOptions)]),
     ("mjh_set_light_active", C.c_int, [_vp, C.c_int, C.c_int]),
+    ("mjh_render_set_texturing", C.c_int, [_vp, C.c_int]),
+    ("mjh_render_get_texturing", C.c_int, [_vp]),
     ("mjh_export_state_device", C.c_int, [_vp, _vp]),
     ("mjh_state_stride", C.c_int, [_vp]),
     ("mjh_mirror_create", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(_vp)]),

@@ -24,6 +24,7 @@ struct LightArgs {
   const float4* color;             // [ngeom] geom_rgba
   const float* normal;             // [n][height][width][3]: the shade launch's normal image, read
   unsigned* rgba;                  // [n][height][width], written
+  const unsigned* texel;           // ShadeArgs::texel: null without texturing
   float ambient, diffuse;
   unsigned background;
   int nlight;                      // the ACTIVE lights, in id order

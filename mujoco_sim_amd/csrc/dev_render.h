@@ -19,7 +19,12 @@ struct ShadeArgs {
   unsigned* rgba;                  // [n][height][width] (R, G, B, A bytes in memory order), may be null
   float ambient, diffuse;
   unsigned background;             // the packed colour of a miss
+  const unsigned* texel;           // [n][height][width] the texture kernel's image (dev_texture.h), null without texturing: a pixel's texel
+                                   // (R, G, B bytes and TEXEL_FLAG) scales its geom's colour; TEXEL_NONE leaves it as it is
 };
+
+#define TEXEL_FLAG 0xff000000u     // the flag byte of a texel word: the pixel's geom carries a texture
+#define TEXEL_NONE 0u              // a miss, or a geom without a texture
 
 hipError_t mjh_launch_shade(hipStream_t st, const ShadeArgs& A);   // render.hip
 
@@ -122,6 +127,13 @@ RDEV unsigned render_level(float c) {
 }
 RDEV unsigned render_pack(float r, float g, float b, float a) {
   return render_level(r) | (render_level(g) << 8) | (render_level(b) << 16) | (render_level(a) << 24);
+}
+// the base colour of a textured pixel: the geom's r, g, b times the texel's bytes / 255 (the quotient and the product rounded
+// separately), the geom's alpha
+RDEV float4 render_texel_base(const float4 col, unsigned t) {
+#pragma clang fp contract(off)
+  const float tr = (float)(t & 0xffu) / 255.0f, tg = (float)((t >> 8) & 0xffu) / 255.0f, tb = (float)((t >> 16) & 0xffu) / 255.0f;
+  return make_float4(col.x * tr, col.y * tg, col.z * tb, col.w);
 }
 // the colour of a hit: the geom's r, g, b times shade = ambient + diffuse * ndv, alpha 255
 RDEV unsigned render_color(const float4 col, float ambient, float diffuse, float ndv) {

@@ -19,6 +19,7 @@
 #include "dev_depth.h"
 #include "dev_render.h"
 #include "dev_light.h"
+#include "dev_texture.h"
 #include "ray_tables.h"
 
 void mjh_set_error(const std::string& s);  // model_builder.cpp
@@ -133,6 +134,9 @@ struct mjh_engine {
   // model once (light_tables); the active mask is applied when a call packs its launch descriptor
   int light_mode = 0; mjh_light_options light_opt = {1, 1, 1e-3f};
   bool lights_ready = false; int nlight = 0; LightRec lights[MJH_MAXLIGHT]; int light_on[MJH_MAXLIGHT];
+  // textures (mjh_render_set_texturing, texture.hip): the mode; the geoms' records and the texels, one word each, uploaded at the first
+  // textured render call (texture_tables); the texel image of a call
+  int tex_mode = 0; TexRec* tex_rec = nullptr; unsigned* tex_data = nullptr; float* tex_io = nullptr; size_t tex_io_floats = 0;
 };
 
 static int pad32(int n) { return ((n + 31) / 32) * 32; }
@@ -808,6 +812,7 @@ extern "C" void mjh_destroy(mjh_engine* e) {
   if (e->scratch) (void)hipFree(e->scratch);
   if (e->ray_io) (void)hipFree(e->ray_io);
   if (e->render_io) (void)hipFree(e->render_io);
+  if (e->tex_io) (void)hipFree(e->tex_io);
   if (e->h_dense) (void)hipHostFree(e->h_dense);
   if (e->h_wn) (void)hipHostFree(e->h_wn);
   if (e->h_io) (void)hipHostFree(e->h_io);
@@ -2216,6 +2221,38 @@ extern "C" int mjh_set_light_active(mjh_engine* e, int light, int on) {
   return MJH_OK;
 }
 
+// ---- textures (include/mjhip.h: mjh_render_set_texturing).  The geoms' texture records and the texel table, once per engine.
+static int texture_tables(mjh_engine* e) {
+  if (e->tex_rec) return MJH_OK;
+  const mjh_model* m = e->model;
+  std::vector<TexRec> rec((size_t)std::max(m->ngeom, 1), TexRec{-1, 0, 1, 1, 1.0f, 1.0f, 0, 0});
+  for (int g = 0; g < m->ngeom; g++) {
+    const int t = m->geom_texid ? m->geom_texid[g] : -1;
+    if (t < 0 || t >= m->ntex) continue;
+    const long long adr = m->tex_adr[t], w = m->tex_width[t], h = m->tex_height[t];
+    if (w < 1 || h < 1 || adr < 0 || adr + w * h > (long long)m->ntexdata) { mjh_set_error("mjh_render: texture table out of range"); return MJH_ERR_ARG; }
+    rec[g] = TexRec{t, (int)adr, (int)w, (int)h, (float)m->geom_texrepeat[2*g], (float)m->geom_texrepeat[2*g+1], m->geom_texuniform[g] ? 1 : 0, 0};
+  }
+  std::vector<unsigned> tex((size_t)m->ntexdata);
+  for (size_t i = 0; i < tex.size(); i++) tex[i] = (unsigned)m->tex_rgb[3*i] | ((unsigned)m->tex_rgb[3*i+1] << 8) | ((unsigned)m->tex_rgb[3*i+2] << 16) | TEXEL_FLAG;
+  TexRec* dr = nullptr; unsigned* dt = nullptr;
+  int rc = dev_alloc(e, &dt, tex.size(), false);
+  if (rc) return rc;
+  rc = dev_alloc(e, &dr, rec.size(), false);
+  if (rc) return rc;
+  HIPCHK(hipMemcpy(dt, tex.data(), tex.size() * sizeof(unsigned), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dr, rec.data(), rec.size() * sizeof(TexRec), hipMemcpyHostToDevice));
+  e->tex_data = dt; e->tex_rec = dr;
+  return MJH_OK;
+}
+extern "C" int mjh_render_set_texturing(mjh_engine* e, int mode) {
+  ENG_NOJOIN(e);
+  if (mode != 0 && mode != 1) { mjh_set_error("mjh_render_set_texturing: mode must be 0 or 1"); return MJH_ERR_ARG; }
+  e->tex_mode = mode;
+  return MJH_OK;
+}
+extern "C" int mjh_render_get_texturing(const mjh_engine* e) { return e ? e->tex_mode : 0; }
+
 extern "C" int mjh_render_device(mjh_engine* e, int env0, int n, const mjh_render_options* opt, float* d_depth, int* d_geomid, float* d_normal, unsigned char* d_rgba) {
   ENG(e);
   mjh_render_options o; mjh_render_default_options(&o);
@@ -2240,15 +2277,32 @@ extern "C" int mjh_render_device(mjh_engine* e, int env0, int n, const mjh_rende
     if (!d_geomid) d_geomid = (int*)(e->render_io + nout);
     if (lit && !d_normal) d_normal = e->render_io + 2 * nout;
   }
+  // texturing mode 1 with a colour image and a textured model: the texture kernel writes the texel image between the depth and shade launches
+  const bool textured = e->tex_mode == 1 && d_rgba && e->model->ntex > 0 && e->model->ntexdata > 0;
+  unsigned* d_texel = nullptr;
+  if (textured) {
+    rc = texture_tables(e);
+    if (rc) return rc;
+    rc = io_reserve(e, &e->tex_io, &e->tex_io_floats, nout);
+    if (rc) return rc;
+    d_texel = (unsigned*)e->tex_io;
+  }
   ShadeArgs A{};
   rc = depth_chain(e, env0, n, o.view, d_depth, d_geomid, &A.D);
   if (rc) return rc;
   HIPCHK(mjh_launch_depth(e->stream, A.D));
+  if (textured) {
+    TextureArgs TA{};
+    TA.D = A.D; TA.rec = e->tex_rec; TA.texels = e->tex_data; TA.ntexdata = e->model->ntexdata; TA.out = d_texel;
+    HIPCHK(mjh_launch_texture(e->stream, TA));
+  }
+  A.texel = lit ? nullptr : d_texel;
   A.color = e->ray_color; A.normal = d_normal; A.rgba = lit ? nullptr : (unsigned*)d_rgba;
   A.ambient = o.ambient; A.diffuse = o.diffuse;
   A.background = render_pack(o.background[0], o.background[1], o.background[2], o.background[3]);
   HIPCHK(mjh_launch_shade(e->stream, A));
   if (lit) {
+    LA.texel = d_texel;
     LA.D = A.D; LA.color = e->ray_color; LA.normal = d_normal; LA.rgba = (unsigned*)d_rgba;
     LA.ambient = o.ambient; LA.diffuse = o.diffuse; LA.background = A.background;
     LA.shadows = e->light_opt.shadows; LA.cull = e->light_opt.cull; LA.bias = e->light_opt.bias;

@@ -202,7 +202,12 @@ __global__ __launch_bounds__(RAY_TILE) void mjh_light_kernel(const LightArgs A) 
   unsigned out = A.background;
   if (hit) {
     const float shade = A.ambient + A.diffuse * light_ndv(n, v, vv);
-    out = light_color(A.color[gid], shade, sum);
+    float4 col = A.color[gid];
+    if (A.texel) {      // (texturing 1: the texture kernel's word of this pixel)
+      const unsigned t = A.texel[q];
+      if (t & TEXEL_FLAG) col = render_texel_base(col, t);
+    }
+    out = light_color(col, shade, sum);
   }
   A.rgba[q] = out;
 }

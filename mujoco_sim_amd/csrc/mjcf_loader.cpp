@@ -110,6 +110,7 @@ static thread_local int g_robot_gravcomp = -1;   // mjh_load_set_robot_gravcomp:
 static thread_local std::map<std::string, std::array<double, 6>> g_robot_pose;   // mjh_load_set_robot_pose: root body name -> x y z roll pitch yaw
 static thread_local unsigned g_odom_mask = 0;      // mjh_load_set_odom_joints: bits 0..5 = lin x y z, ang x y z
 static thread_local int g_pc_exclude_level = 0;   // mjh_load_set_parent_child_exclude: a body does not collide with its first k ancestors (mujoco_compile.cpp:250-290)
+static thread_local int g_load_textures = 0; // mjh_load_set_textures: 0 = <texture> is not read (a material's texture is noted and dropped), 1 = builtin 2D textures are loaded
 static thread_local int g_load_meshes = 1;   // mjh_load_set_mesh_mode: 0 = skip mesh assets (their geoms are reported and dropped)
 
 struct Loader {
@@ -120,6 +121,10 @@ struct Loader {
   Defaults def;
   std::map<std::string, int> body_id, joint_id, mesh_id, site_id, hfield_id;
   std::map<std::string, std::array<double, 4>> material_rgba;   // <asset><material name rgba>: colour only, per file like the meshes
+  // textures (mjh_load_set_textures 1): <asset><texture> name -> builder id, and what a material carries to its geoms; per file
+  struct MatTex { int tex = -1; double repeat[2] = {1, 1}; int uniform = 0; };
+  std::map<std::string, int> texture_id;
+  std::map<std::string, MatTex> material_tex;
   std::vector<int> body_parent;      // parent body of every body added so far
   // <default class="..."> tables: class -> element tag -> attributes (a nested class starts from its parent's); the
   // unnamed top-level <default> is class "main".  An element takes the attributes it does not set itself from its class
@@ -230,6 +235,14 @@ struct Loader {
       if (gid < 0) return false;
     } else gid = mjh_builder_add_geom(b, n.get("name"), body, gt, size, pos, quat, fr, condim, contype, conaff, density);
     if (coloured && gid >= 0 && mjh_builder_set_geom_rgba(b, gid, rgba) < 0) return false;
+    // texture: the material's, whichever colour won above
+    if (g_load_textures && gid >= 0 && n.get("material")) {
+      auto it = material_tex.find(n.get("material"));
+      if (it != material_tex.end() && it->second.tex >= 0) {
+        if (gt == MJH_GEOM_MESH) note += std::string("ignored texture of material ") + n.get("material") + " on mesh geom " + (n.get("name") ? n.get("name") : "(unnamed)") + " (mesh texture coordinates are not kept: plain colour); ";
+        else if (mjh_builder_set_geom_texture(b, gid, it->second.tex, it->second.repeat, it->second.uniform) < 0) return false;
+      }
+    }
     return true;
   }
   bool joint(const Node& n0, int body, bool freejoint) {
@@ -371,7 +384,7 @@ struct Loader {
     if (root.tag != "mujoco") { mjh_set_error("root element must be <mujoco>"); return false; }
     if (first) b = mjh_builder_create();
     robot_file = !first;      // files after the world file are robots (MjSim::init composition)
-    degree = true; autolimits = false; def = Defaults(); basedir = dir; meshdir.clear(); mesh_id.clear(); hfield_id.clear(); material_rgba.clear(); classes.clear(); childclass.clear();
+    degree = true; autolimits = false; def = Defaults(); basedir = dir; meshdir.clear(); mesh_id.clear(); hfield_id.clear(); material_rgba.clear(); texture_id.clear(); material_tex.clear(); classes.clear(); childclass.clear();
     mjh_option o; mjh_builder_get_option(b, &o);
     bool solver_named = false;
     // first pass: compiler / option / default (they may appear after worldbody in a file)
@@ -482,6 +495,29 @@ struct Loader {
       if (id < 0) { mjh_set_error("hfield " + name + ": " + mjh_last_error()); return false; }
       hfield_id[name] = id;
     }
+    // <asset><texture> (mjh_load_set_textures 1): builtin 2D textures; everything else is skipped with a note and the geoms keep their
+    // plain colour.  [UPSTREAM, unverified here] MuJoCo's defaults: type cube, builtin none, mark none, height = width for 2D builtins
+    if (g_load_textures) for (auto& c : root.kids) if (c->tag == "asset") for (auto& a : c->kids) if (a->tag == "texture") {
+      const Node t = with_defaults(*a);
+      std::string name = t.get("name") ? t.get("name") : "";
+      if (name.empty() && t.get("file")) { std::string fn = t.get("file"); size_t sl = fn.find_last_of('/'), dot = fn.find_last_of('.'); name = fn.substr(sl == std::string::npos ? 0 : sl + 1, dot == std::string::npos ? std::string::npos : dot - (sl == std::string::npos ? 0 : sl + 1)); }
+      const std::string type = t.get("type") ? t.get("type") : "cube", builtin = t.get("builtin") ? t.get("builtin") : "none", mark = t.get("mark") ? t.get("mark") : "none";
+      if (type != "2d") { note += "skipped <texture " + name + " type=\"" + type + "\"> (only 2d textures are loaded); "; continue; }
+      if (builtin == "none") { note += "skipped <texture " + name + "> (" + (t.get("file") ? "file textures are not supported: no image decoder" : "neither builtin nor file") + "); "; continue; }
+      const int bi = builtin == "flat" ? MJH_TEXBUILTIN_FLAT : builtin == "checker" ? MJH_TEXBUILTIN_CHECKER : builtin == "gradient" ? MJH_TEXBUILTIN_GRADIENT : -1;
+      if (bi < 0) { note += "skipped <texture " + name + " builtin=\"" + builtin + "\"> (flat, checker and gradient are generated); "; continue; }
+      if (mark == "random") { note += "skipped <texture " + name + " mark=\"random\"> (it needs MuJoCo's random generator); "; continue; }
+      const int mk = mark == "none" ? MJH_TEXMARK_NONE : mark == "edge" ? MJH_TEXMARK_EDGE : mark == "cross" ? MJH_TEXMARK_CROSS : -1;
+      if (mk < 0) { note += "skipped <texture " + name + " mark=\"" + mark + "\"> (none, edge and cross are generated); "; continue; }
+      double w = 0, h = 0, rgb1[3] = {0.8, 0.8, 0.8}, rgb2[3] = {0.5, 0.5, 0.5}, markrgb[3] = {0, 0, 0};
+      nums(t.get("width"), &w, 1);
+      if (!nums(t.get("height"), &h, 1)) h = w;
+      nums(t.get("rgb1"), rgb1, 3); nums(t.get("rgb2"), rgb2, 3); nums(t.get("markrgb"), markrgb, 3);
+      const int wi = w >= 0 && w <= 1e9 ? (int)w : -1, hi = h >= 0 && h <= 1e9 ? (int)h : -1;
+      const int id = mjh_builder_add_texture_builtin(b, name.c_str(), bi, mk, wi, hi, rgb1, rgb2, markrgb);
+      if (id < 0) { note += "skipped <texture " + name + "> (" + mjh_last_error() + "); "; continue; }
+      texture_id[name] = id;
+    }
     // <asset><material name rgba>: the colour a geom with material= takes unless it has an rgba of its own; a material without rgba is
     // white [UPSTREAM, unverified here: MuJoCo's material default is 1 1 1 1]
     for (auto& c : root.kids) if (c->tag == "asset") for (auto& a : c->kids) if (a->tag == "material") {
@@ -495,7 +531,22 @@ struct Loader {
         if (ok) col = c;
         else note += std::string("ignored rgba of material ") + mn.get("name") + " (not four numbers in [0, 1]: white); ";
       }
-      for (auto& at : mn.attr) if (at.first != "name" && at.first != "rgba" && at.first != "class")
+      if (g_load_textures) {      // texture, texrepeat, texuniform go to the geoms that name the material
+        MatTex mt;
+        if (const char* tn = mn.get("texture")) {
+          auto it = texture_id.find(tn);
+          if (it == texture_id.end()) note += std::string("material ") + mn.get("name") + ": texture " + tn + " not loaded (plain colour); ";
+          else mt.tex = it->second;
+        }
+        double r[2];
+        if (mn.get("texrepeat")) {
+          if (nums(mn.get("texrepeat"), r, 2) == 2 && r[0] > 0.0 && r[1] > 0.0 && std::isfinite(r[0]) && std::isfinite(r[1])) { mt.repeat[0] = r[0]; mt.repeat[1] = r[1]; }
+          else note += std::string("ignored texrepeat of material ") + mn.get("name") + " (not two positive numbers: 1 1); ";
+        }
+        if (const char* u = mn.get("texuniform")) mt.uniform = std::string(u) == "true";
+        material_tex[mn.get("name")] = mt;
+      }
+      for (auto& at : mn.attr) if (at.first != "name" && at.first != "rgba" && at.first != "class" && !(g_load_textures && (at.first == "texture" || at.first == "texrepeat" || at.first == "texuniform")))
         note += "ignored material attribute " + at.first + " of " + mn.get("name") + " (colour only); ";
       material_rgba[mn.get("name")] = col;
     }
@@ -641,7 +692,7 @@ extern "C" mjh_model* mjh_load_mjcf_files(const char* const* paths, int n) {
 // the same with the options of THIS call only (the rosparams MjSim::init_tmp reads: mj_sim.cpp:301-415,584-590)
 extern "C" mjh_model* mjh_load_mjcf_files_opt(const char* const* paths, int n, const mjh_load_options* o) {
   if (!o) return mjh_load_mjcf_files(paths, n);
-  const double sb = g_boundmass, si = g_boundinertia; const int sg = g_robot_gravcomp, sm = g_load_meshes; const unsigned so = g_odom_mask;
+  const double sb = g_boundmass, si = g_boundinertia; const int sg = g_robot_gravcomp, sm = g_load_meshes, st = g_load_textures; const unsigned so = g_odom_mask;
   const auto sp = g_robot_pose; const int sx = g_pc_exclude_level;
   g_pc_exclude_level = o->parent_child_exclude < 0 ? 0 : o->parent_child_exclude;
   g_boundmass = o->boundmass; g_boundinertia = o->boundinertia; g_robot_gravcomp = o->robot_gravcomp < 0 ? -1 : (o->robot_gravcomp ? 1 : 0);
@@ -652,7 +703,7 @@ extern "C" mjh_model* mjh_load_mjcf_files_opt(const char* const* paths, int n, c
     g_robot_pose[o->robot_pose_body[k]] = a;
   }
   mjh_model* m = mjh_load_mjcf_files(paths, n);
-  g_boundmass = sb; g_boundinertia = si; g_robot_gravcomp = sg; g_load_meshes = sm; g_odom_mask = so; g_robot_pose = sp; g_pc_exclude_level = sx;
+  g_boundmass = sb; g_boundinertia = si; g_robot_gravcomp = sg; g_load_meshes = sm; g_load_textures = st; g_odom_mask = so; g_robot_pose = sp; g_pc_exclude_level = sx;
   return m;
 }
 extern "C" void mjh_load_default_options(mjh_load_options* o) {
@@ -662,6 +713,7 @@ extern "C" void mjh_load_default_options(mjh_load_options* o) {
 extern "C" const char* mjh_load_note(void) { return g_note.c_str(); }
 extern "C" void mjh_load_set_bounds(double boundmass, double boundinertia) { g_boundmass = boundmass; g_boundinertia = boundinertia; }
 extern "C" void mjh_load_set_mesh_mode(int mode) { g_load_meshes = mode != 0; }
+extern "C" void mjh_load_set_textures(int mode) { g_load_textures = mode != 0; }
 extern "C" void mjh_load_set_robot_pose(const char* root_body, const double pose[6]) {
   if (!root_body) { g_robot_pose.clear(); return; }
   if (!pose) { g_robot_pose.erase(root_body); return; }

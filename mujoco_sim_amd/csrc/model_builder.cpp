@@ -33,6 +33,7 @@ struct BGeom {
   std::string name; int body, type; double size[3], pos[3], quat[4], friction[3];
   int condim, contype, conaffinity; double density; int mesh = -1; int hfield = -1;
   double rgba[4] = {0.5, 0.5, 0.5, 1.0};      // [UPSTREAM, unverified here] MuJoCo's geom default
+  int tex = -1; double texrepeat[2] = {1.0, 1.0}; int texuniform = 0;   // the material's texture (mjh_builder_set_geom_texture)
 };
 // height field asset: elevation grid as given (normalised at compile time)
 struct BHField { std::string name; int nrow, ncol; double size[4]; std::vector<double> data; };
@@ -50,6 +51,7 @@ struct BEq { int type = MJH_EQ_JOINT; int j1 = -1, j2 = -1; double poly[5] = {0,
 struct BSite { std::string name; int body; double pos[3], quat[4]; };
 struct BSensor { std::string name; int type, site; };
 struct BCamera { std::string name; int body; double pos[3], quat[4], fovy; };
+struct BTexture { std::string name; int width, height; std::vector<unsigned char> rgb; };   // 3 width height bytes, row 0 first
 struct BLight { std::string name; int body, directional, castshadow, active; double pos[3], dir[3], diffuse[3], ambient[3], cutoff, exponent; };
 
 }  // namespace
@@ -70,6 +72,7 @@ struct mjh_builder {
   std::vector<BSensor> sensors;
   std::vector<BCamera> cameras;
   std::vector<BLight> lights;
+  std::vector<BTexture> textures; long long ntexel = 0;   // texels of all textures so far
   std::vector<int> mocap;       // builder body ids flagged <body mocap="true">
 };
 
@@ -601,6 +604,58 @@ extern "C" int mjh_builder_add_light(mjh_builder* b, const char* name, int body,
 extern "C" int mjh_builder_set_light_active(mjh_builder* b, int light, int on) {
   if (!b || light < 0 || light >= (int)b->lights.size()) { g_err = "set_light_active: bad light"; return MJH_ERR_ARG; }
   b->lights[light].active = on ? 1 : 0;
+  return MJH_OK;
+}
+// ---- textures (include/mjhip.h states the limits and the builtin definitions)
+static bool texture_room(mjh_builder* b, const char* who, int width, int height) {
+  if (!b) { g_err = std::string(who) + ": null builder"; return false; }
+  if (width < 1 || width > MJH_MAXTEXSIZE || height < 1 || height > MJH_MAXTEXSIZE) { g_err = std::string(who) + ": width and height must lie in 1 ... MJH_MAXTEXSIZE (4096)"; return false; }
+  if (b->ntexel + (long long)width * height > (long long)MJH_MAXTEXDATA) { g_err = std::string(who) + ": the textures of a model hold at most MJH_MAXTEXDATA (2^24) texels"; return false; }
+  return true;
+}
+extern "C" int mjh_builder_add_texture(mjh_builder* b, const char* name, int width, int height, const unsigned char* rgb) {
+  if (!texture_room(b, "add_texture", width, height)) return MJH_ERR_ARG;
+  if (!rgb) { g_err = "add_texture: null texels"; return MJH_ERR_ARG; }
+  BTexture t; t.name = name ? name : ""; t.width = width; t.height = height; t.rgb.assign(rgb, rgb + (size_t)3 * width * height);
+  b->ntexel += (long long)width * height;
+  b->textures.push_back(std::move(t)); return (int)b->textures.size() - 1;
+}
+extern "C" int mjh_builder_add_texture_builtin(mjh_builder* b, const char* name, int builtin, int mark, int width, int height,
+                                               const double rgb1[3], const double rgb2[3], const double markrgb[3]) {
+  if (!texture_room(b, "add_texture_builtin", width, height)) return MJH_ERR_ARG;
+  if (builtin < MJH_TEXBUILTIN_FLAT || builtin > MJH_TEXBUILTIN_GRADIENT) { g_err = "add_texture_builtin: builtin must be flat, checker or gradient"; return MJH_ERR_ARG; }
+  if (mark < MJH_TEXMARK_NONE || mark > MJH_TEXMARK_CROSS) { g_err = "add_texture_builtin: mark must be none, edge or cross"; return MJH_ERR_ARG; }
+  // [UPSTREAM, unverified here] MuJoCo's texture defaults: rgb1 0.8 0.8 0.8, rgb2 0.5 0.5 0.5, markrgb 0 0 0
+  double c1[3], c2[3], cm[3];
+  for (int k = 0; k < 3; k++) { c1[k] = rgb1 ? rgb1[k] : 0.8; c2[k] = rgb2 ? rgb2[k] : 0.5; cm[k] = markrgb ? markrgb[k] : 0.0; }
+  for (int k = 0; k < 3; k++) if (!(c1[k] >= 0.0 && c1[k] <= 1.0 && c2[k] >= 0.0 && c2[k] <= 1.0 && cm[k] >= 0.0 && cm[k] <= 1.0)) { g_err = "add_texture_builtin: colour components must lie in [0, 1]"; return MJH_ERR_ARG; }
+  auto byte = [](double c) { return (unsigned char)(int)(255.0 * c + 0.5); };
+  const int W = width, H = height;
+  BTexture t; t.name = name ? name : ""; t.width = W; t.height = H; t.rgb.resize((size_t)3 * W * H);
+  for (int j = 0; j < H; j++) for (int i = 0; i < W; i++) {
+    unsigned char* px = &t.rgb[((size_t)j * W + i) * 3];
+    double r = 0.0;   // the weight of rgb2
+    if (builtin == MJH_TEXBUILTIN_CHECKER) r = ((j < H / 2) == (i < W / 2)) ? 0.0 : 1.0;
+    else if (builtin == MJH_TEXBUILTIN_GRADIENT) {
+      const double x = W > 1 ? 2.0 * i / (W - 1) - 1.0 : 0.0, y = H > 1 ? 2.0 * j / (H - 1) - 1.0 : 0.0;
+      r = std::min(1.0, std::sqrt(x * x + y * y));
+    }
+    for (int k = 0; k < 3; k++) px[k] = byte(c1[k] * (1.0 - r) + c2[k] * r);
+    const bool marked = mark == MJH_TEXMARK_EDGE ? (j == 0 || j == H - 1 || i == 0 || i == W - 1) : mark == MJH_TEXMARK_CROSS ? (j == H / 2 || i == W / 2) : false;
+    if (marked) for (int k = 0; k < 3; k++) px[k] = byte(cm[k]);
+  }
+  b->ntexel += (long long)W * H;
+  b->textures.push_back(std::move(t)); return (int)b->textures.size() - 1;
+}
+extern "C" int mjh_builder_set_geom_texture(mjh_builder* b, int geom, int tex, const double texrepeat[2], int texuniform) {
+  if (!b || geom < 0 || geom >= (int)b->geoms.size()) { g_err = "set_geom_texture: bad geom"; return MJH_ERR_ARG; }
+  BGeom& G = b->geoms[geom];
+  if (tex == -1) { G.tex = -1; G.texrepeat[0] = G.texrepeat[1] = 1.0; G.texuniform = 0; return MJH_OK; }
+  if (tex < 0 || tex >= (int)b->textures.size()) { g_err = "set_geom_texture: bad texture"; return MJH_ERR_ARG; }
+  if (G.type == MJH_GEOM_MESH) { g_err = "set_geom_texture: a mesh geom takes no texture (its texture coordinates are not kept)"; return MJH_ERR_ARG; }
+  const double r[2] = {texrepeat ? texrepeat[0] : 1.0, texrepeat ? texrepeat[1] : 1.0};
+  if (!(r[0] > 0.0 && std::isfinite(r[0]) && r[1] > 0.0 && std::isfinite(r[1]))) { g_err = "set_geom_texture: texrepeat must be finite and > 0"; return MJH_ERR_ARG; }
+  G.tex = tex; G.texrepeat[0] = r[0]; G.texrepeat[1] = r[1]; G.texuniform = texuniform ? 1 : 0;
   return MJH_OK;
 }
 extern "C" int mjh_builder_set_geom_rgba(mjh_builder* b, int geom, const double rgba[4]) {
@@ -1227,6 +1282,23 @@ extern "C" mjh_model* mjh_builder_compile(mjh_builder* B) {
     m->light_diffuse = dup(diffuse); m->light_ambient = dup(ambient); m->light_cutoff = dup(cutoff); m->light_exponent = dup(exponent);
     m->light_names = dupnames(names);
   }
+  {   // textures: the texels of all textures in one table; the geoms' records follow the compile step's geom order
+    const int nt = (int)B->textures.size();
+    std::vector<int> width(nt), height(nt), adr(nt), texid(ngeom), uniform(ngeom); std::vector<double> repeat(2 * (size_t)ngeom);
+    std::vector<unsigned char> rgb; std::vector<std::string> names(nt);
+    for (int t = 0; t < nt; t++) {
+      const BTexture& T = B->textures[t];
+      width[t] = T.width; height[t] = T.height; adr[t] = (int)(rgb.size() / 3); names[t] = T.name;
+      rgb.insert(rgb.end(), T.rgb.begin(), T.rgb.end());
+    }
+    for (int g = 0; g < ngeom; g++) {
+      const BGeom& G = B->geoms[gorder[g]];
+      texid[g] = G.tex; repeat[2*g] = G.texrepeat[0]; repeat[2*g+1] = G.texrepeat[1]; uniform[g] = G.texuniform;
+    }
+    m->ntex = nt; m->ntexdata = (int)(rgb.size() / 3);
+    m->tex_width = dup(width); m->tex_height = dup(height); m->tex_adr = dup(adr); m->tex_rgb = dup(rgb); m->tex_names = dupnames(names);
+    m->geom_texid = dup(texid); m->geom_texrepeat = dup(repeat); m->geom_texuniform = dup(uniform);
+  }
   return m;
 }
 
@@ -1237,6 +1309,7 @@ extern "C" mjh_model* mjh_model_replicate(const mjh_model* a, int G) {
   if (a->nhfield > 0) { g_err = "mjh_model_replicate: models with height fields are not packed"; return nullptr; }
   if (a->ncam > 0) { g_err = "mjh_model_replicate: models with cameras are not packed"; return nullptr; }
   if (a->nlight > 0) { g_err = "mjh_model_replicate: models with lights are not packed"; return nullptr; }
+  if (a->ntex > 0) { g_err = "mjh_model_replicate: models with textures are not packed"; return nullptr; }
   for (int e = 0; e < a->neq; e++) if (a->eq_type[e] != MJH_EQ_JOINT) { g_err = "mjh_model_replicate: connect / weld equalities are not packed"; return nullptr; }
   const int nb = a->nbody, nj = a->njnt, nv = a->nv, nq = a->nq, ng = a->ngeom, nt = a->ntree, ne = a->neq, np = a->npair, nM = a->nM;
   std::vector<int> moving_b, moving_g;
@@ -1376,27 +1449,28 @@ extern "C" void mjh_model_destroy(mjh_model* m) {
     m->mesh_planeadr, m->mesh_planenum, m->mesh_plane, m->cam_bodyid, m->cam_pos, m->cam_quat, m->cam_fovy,
     m->mesh_triadr, m->mesh_trinum, m->mesh_tri, m->geom_rgba,
     m->light_bodyid, m->light_pos, m->light_dir, m->light_directional, m->light_castshadow, m->light_active,
-    m->light_diffuse, m->light_ambient, m->light_cutoff, m->light_exponent};
+    m->light_diffuse, m->light_ambient, m->light_cutoff, m->light_exponent,
+    m->tex_width, m->tex_height, m->tex_adr, m->tex_rgb, m->geom_texid, m->geom_texrepeat, m->geom_texuniform};
   for (void* p : ptrs) std::free(p);
   auto freen = [](char** n, int c) { if (!n) return; for (int i = 0; i < c; i++) std::free(n[i]); std::free(n); };
   freen(m->body_names, m->nbody); freen(m->jnt_names, m->njnt); freen(m->geom_names, m->ngeom);
   freen(m->site_names, m->nsite); freen(m->sensor_names, m->nsensor); freen(m->hfield_names, m->nhfield);
-  freen(m->cam_names, m->ncam); freen(m->light_names, m->nlight);
+  freen(m->cam_names, m->ncam); freen(m->light_names, m->nlight); freen(m->tex_names, m->ntex);
   std::free(m);
 }
 
 extern "C" int mjh_name2id(const mjh_model* m, int objtype, const char* name) {
   if (!m || !name) return -1;
-  char** t = objtype == 0 ? m->body_names : objtype == 1 ? m->jnt_names : objtype == 2 ? m->geom_names : objtype == 3 ? m->site_names : objtype == 5 ? m->cam_names : objtype == 6 ? m->light_names : m->sensor_names;
-  int n = objtype == 0 ? m->nbody : objtype == 1 ? m->njnt : objtype == 2 ? m->ngeom : objtype == 3 ? m->nsite : objtype == 5 ? m->ncam : objtype == 6 ? m->nlight : m->nsensor;
-  if (!t || objtype < 0 || objtype > 6) return -1;     // a model assembled without name tables
+  char** t = objtype == 0 ? m->body_names : objtype == 1 ? m->jnt_names : objtype == 2 ? m->geom_names : objtype == 3 ? m->site_names : objtype == 5 ? m->cam_names : objtype == 6 ? m->light_names : objtype == 7 ? m->tex_names : m->sensor_names;
+  int n = objtype == 0 ? m->nbody : objtype == 1 ? m->njnt : objtype == 2 ? m->ngeom : objtype == 3 ? m->nsite : objtype == 5 ? m->ncam : objtype == 6 ? m->nlight : objtype == 7 ? m->ntex : m->nsensor;
+  if (!t || objtype < 0 || objtype > 7) return -1;     // a model assembled without name tables
   for (int i = 0; i < n; i++) if (t[i] && std::strcmp(t[i], name) == 0) return i;
   return -1;
 }
 extern "C" const char* mjh_id2name(const mjh_model* m, int objtype, int id) {
   if (!m) return nullptr;
-  char** t = objtype == 0 ? m->body_names : objtype == 1 ? m->jnt_names : objtype == 2 ? m->geom_names : objtype == 3 ? m->site_names : objtype == 5 ? m->cam_names : objtype == 6 ? m->light_names : m->sensor_names;
-  int n = objtype == 0 ? m->nbody : objtype == 1 ? m->njnt : objtype == 2 ? m->ngeom : objtype == 3 ? m->nsite : objtype == 5 ? m->ncam : objtype == 6 ? m->nlight : m->nsensor;
-  if (!t || objtype < 0 || objtype > 6 || id < 0 || id >= n) return nullptr;
+  char** t = objtype == 0 ? m->body_names : objtype == 1 ? m->jnt_names : objtype == 2 ? m->geom_names : objtype == 3 ? m->site_names : objtype == 5 ? m->cam_names : objtype == 6 ? m->light_names : objtype == 7 ? m->tex_names : m->sensor_names;
+  int n = objtype == 0 ? m->nbody : objtype == 1 ? m->njnt : objtype == 2 ? m->ngeom : objtype == 3 ? m->nsite : objtype == 5 ? m->ncam : objtype == 6 ? m->nlight : objtype == 7 ? m->ntex : m->nsensor;
+  if (!t || objtype < 0 || objtype > 7 || id < 0 || id >= n) return nullptr;
   return t[id];
 }

@@ -66,6 +66,10 @@ __global__ __launch_bounds__(RAY_TILE) void mjh_shade_kernel(const ShadeArgs A) 
   const float ndv = render_finish(n, v, vv);
   const size_t q = ((size_t)row * (size_t)D.height + (size_t)pi) * (size_t)D.width + (size_t)pj;
   if (A.normal) { A.normal[3*q] = n[0]; A.normal[3*q + 1] = n[1]; A.normal[3*q + 2] = n[2]; }
+  if (A.texel && A.rgba && gid >= 0) {      // (texturing 1: the texture kernel's word of this pixel)
+    const unsigned t = A.texel[q];
+    if (t & TEXEL_FLAG) col = render_texel_base(col, t);
+  }
   if (A.rgba) A.rgba[q] = gid >= 0 ? render_color(col, A.ambient, A.diffuse, ndv) : A.background;
 }
 

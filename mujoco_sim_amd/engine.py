@@ -31,7 +31,7 @@ class Model:
 
     def __getattr__(self, name):
         c = self.__dict__.get("c")
-        if c is not None and name in capi._INT_SIZES + capi._INT_SIZES2 + capi._INT_SIZES4 + capi._INT_SIZES6 + capi._INT_SIZES7 + capi._INT_SIZES9 + ["meaninertia", "opt"]:
+        if c is not None and name in capi._INT_SIZES + capi._INT_SIZES2 + capi._INT_SIZES4 + capi._INT_SIZES6 + capi._INT_SIZES7 + capi._INT_SIZES9 + capi._INT_SIZES10 + ["meaninertia", "opt"]:
             return getattr(c, name)
         raise AttributeError(name)
 
@@ -77,14 +77,21 @@ def boxes_randomize(model, env0, nenv, seed_base=0x5EED0000, jitter=0.01):
     return out
 
 
-def load_mjcf(xml=None, path=None, paths=None):
-    """MJCF-subset loader (mj_loadXML boundary, mj_util.h:185-193); `paths`: world file + robot files composed into one model"""
+def load_mjcf(xml=None, path=None, paths=None, textures=False):
+    """MJCF-subset loader (mj_loadXML boundary, mj_util.h:185-193); `paths`: world file + robot files composed into one model;
+    `textures`: load builtin 2D textures for this call (mjh_load_set_textures 1; the thread's setting is 0 again afterwards)"""
     lib = capi.load()
-    if paths:
-        arr = (C.c_char_p * len(paths))(*[p.encode() for p in paths])
-        ptr = lib.mjh_load_mjcf_files(arr, len(paths))
-    else:
-        ptr = lib.mjh_load_mjcf_file(path.encode()) if path else lib.mjh_load_mjcf_string(xml.encode())
+    if textures:
+        lib.mjh_load_set_textures(1)
+    try:
+        if paths:
+            arr = (C.c_char_p * len(paths))(*[p.encode() for p in paths])
+            ptr = lib.mjh_load_mjcf_files(arr, len(paths))
+        else:
+            ptr = lib.mjh_load_mjcf_file(path.encode()) if path else lib.mjh_load_mjcf_string(xml.encode())
+    finally:
+        if textures:
+            lib.mjh_load_set_textures(0)
     m = Model(ptr, lib)
     m.note = lib.mjh_load_note().decode()
     return m
@@ -462,6 +469,17 @@ class Engine:
         cur.update(options)
         o = capi.LightOptions(int(cur["shadows"]), int(cur["cull"]), float(cur["bias"]))
         _chk(self.lib, self.lib.mjh_render_set_light_options(self.h, C.byref(o)), "mjh_render_set_light_options")
+
+    # ---- textures in the colour image
+    @property
+    def render_texturing(self):
+        """0: a geom's base colour is its geom_rgba (the default); 1: where the geom carries a texture the base colour is geom_rgba
+        times the texel sampled at the hit point (mjh_render_set_texturing)"""
+        return self.lib.mjh_render_get_texturing(self.h)
+
+    @render_texturing.setter
+    def render_texturing(self, mode):
+        _chk(self.lib, self.lib.mjh_render_set_texturing(self.h, int(mode)), "mjh_render_set_texturing")
 
     def set_light_active(self, light, on):
         """switch light `light` (id or name) for every env of the engine, from the next render call on"""
