@@ -611,6 +611,44 @@ int mjh_depth_device(mjh_engine*, int env0, int n, const mjh_depth_options*, flo
 /* host pointers (fp32 images; geomid may be NULL): calls the device form through an engine-owned staging buffer and synchronises */
 int mjh_depth(mjh_engine*, int env0, int n, const mjh_depth_options*, float* depth, int* geomid);
 
+/* Lidar range images: every env's scan from a site of the model — a planar laser (height = 1), a tilt laser's sweep, a spinning 3D
+ * lidar — as range / geom-id images and point clouds.  A camera cannot stand in for a scanner: a pinhole projection ends below 180
+ * degrees, a scan covers 360 of azimuth, and its rows are beam elevations.  The beams are generated on the device from the pattern and
+ * the site's pose in each env: no ray buffer is uploaded, and a scanner on a moving body follows it per env.
+ *   Beam (i, j) — row i, column j — starts at the site's origin and has, in the sensor frame (+x is azimuth 0, +z the rotation axis,
+ *   azimuth counter-clockwise about +z), the direction d = (cos el_i cos az_j, cos el_i sin az_j, sin el_i) with az_j = azimuth0 +
+ *   j azimuth_step and el_i = elevation[i], or elevation0 + i elevation_step without a table.  d is a unit vector up to rounding: the
+ *   host takes cos / sin of every column azimuth and row elevation in fp64 and rounds each to fp32 once; the device multiplies.
+ *   range: the Euclidean distance from the site's origin to the nearest visible surface along the beam; a miss is range -1, geomid -1.
+ *   points: range d in the SENSOR frame (what a sensor_msgs/PointCloud2 of the scanner's frame holds); a miss is (0, 0, 0).
+ *   Everything else is mjh_ray's on the same engine: the semantics per geom type (a scanner inside a geom sees its far surface),
+ *   inactive slots, per-env geom sizes, mjh_ray_set_mesh_mode and mjh_ray_set_mesh_surface, the lower geom id on an exact fp32 tie,
+ *   and the call-sequence rules (a pending mjh_step1 goes out first, a window hand-over is dropped).  Nothing of state, statistics,
+ *   warm start or time is written.
+ *   cull: a wavefront casts a tile of 64 beams (1 x 64 for a planar scan, up to 8 x 8) and walks only the bounded geoms whose
+ *   bounding sphere touches the cone over the tile's beams; a tile that spans more than 180 degrees of azimuth gets no cone.
+ *   cull = 0 makes every tile visit every geom.  The two give the same bits (the cull may never cost a hit).
+ *   The angle tables, 2 (width + height) floats, live in an engine-owned device buffer and are uploaded (in stream order, from an
+ *   engine-owned host buffer) only when the pattern differs from the last call's; `elevation` is read during the call only.
+ * A site or body id out of range, a non-positive size (or n * width * height of 2^30 or more), an angle that is not finite, a row
+ * outside [-pi/2, pi/2], an env range out of bounds or a NULL range pointer return MJH_ERR_ARG and launch nothing. */
+typedef struct mjh_scan_options {
+  int site;                 /* sensor frame: +x is azimuth 0, +z the rotation axis, azimuth counter-clockwise about +z; -1: world frame */
+  int width, height;        /* beams per row (azimuth steps) and rows (elevations); n*width*height below 2^30 */
+  double azimuth0, azimuth_step;     /* column j looks at azimuth0 + j*azimuth_step (radians) */
+  const double* elevation;           /* [height] radians in [-pi/2, pi/2], any order (real lidars are not uniform); NULL: */
+  double elevation0, elevation_step; /*   row i looks at elevation0 + i*elevation_step */
+  int bodyexclude, flg_static;       /* as mjh_ray_options */
+  int cull;                 /* 1 (default): tile culling; 0: every tile visits every geom -- same bits */
+  double cutoff;            /* > 0: a range beyond it is a miss (the scanner's maximum range) */
+} mjh_scan_options;
+void mjh_scan_default_options(mjh_scan_options*);   /* -1, 360, 1, -pi, 2 pi / 360, NULL, 0, 0, -1, 1, 1, 0: one planar turn in 1-degree steps */
+/* device pointers; enqueued on the engine's stream, no synchronisation; d_geomid and d_points may be NULL.  options may be NULL */
+int mjh_scan_device(mjh_engine*, int env0, int n, const mjh_scan_options*,
+                    float* d_range /*[n][height][width]*/, int* d_geomid /*or NULL*/, float* d_points /*[n][height][width][3] or NULL*/);
+/* host pointers (fp32; geomid and points may be NULL): calls the device form through the engine-owned staging buffer and synchronises */
+int mjh_scan(mjh_engine*, int env0, int n, const mjh_scan_options*, float* range, int* geomid, float* points);
+
 /* RGB-D images: beside mjh_depth's depth and geom id, the world-frame surface normal at every pixel's hit and a shaded colour image.
  * Two launches on the engine's stream: the depth launch exactly as mjh_depth_device issues it (so depth and geomid are mjh_depth's
  * bits), then a shading kernel that reads those two images, regenerates each pixel's ray and resolves the normal on the one geom

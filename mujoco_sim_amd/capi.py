@@ -166,6 +166,11 @@ class DepthOptions(C.Structure):
     _fields_ = [("camera", C.c_int), ("width", C.c_int), ("height", C.c_int), ("bodyexclude", C.c_int), ("flg_static", C.c_int),
                 ("range", C.c_int), ("cull", C.c_int), ("cutoff", C.c_double)]
 
+class ScanOptions(C.Structure):
+    _fields_ = [("site", C.c_int), ("width", C.c_int), ("height", C.c_int), ("azimuth0", C.c_double), ("azimuth_step", C.c_double),
+                ("elevation", c_double_p), ("elevation0", C.c_double), ("elevation_step", C.c_double), ("bodyexclude", C.c_int),
+                ("flg_static", C.c_int), ("cull", C.c_int), ("cutoff", C.c_double)]
+
 class LightOptions(C.Structure):
     _fields_ = [("shadows", C.c_int), ("cull", C.c_int), ("bias", C.c_float)]
 
@@ -282,6 +287,9 @@ SYMBOLS = [
     ("mjh_depth_default_options", None, [C.POINTER(DepthOptions)]),
     ("mjh_depth", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(DepthOptions), _vp, _vp]),
     ("mjh_depth_device", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(DepthOptions), _vp, _vp]),
+    ("mjh_scan_default_options", None, [C.POINTER(ScanOptions)]),
+    ("mjh_scan", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(ScanOptions), _vp, _vp, _vp]),
+    ("mjh_scan_device", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(ScanOptions), _vp, _vp, _vp]),
     ("mjh_render_default_options", None, [C.POINTER(RenderOptions)]),
     ("mjh_render", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(RenderOptions), _vp, _vp, _vp, _vp]),
     ("mjh_render_device", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(RenderOptions), _vp, _vp, _vp, _vp]),

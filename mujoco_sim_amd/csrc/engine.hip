@@ -17,6 +17,7 @@
 #include "step_kernel.h"
 #include "dev_ray.h"
 #include "dev_depth.h"
+#include "dev_scan.h"
 #include "dev_render.h"
 #include "dev_light.h"
 #include "dev_texture.h"
@@ -137,6 +138,11 @@ struct mjh_engine {
   // textures (mjh_render_set_texturing, texture.hip): the mode; the geoms' records and the texels, one word each, uploaded at the first
   // textured render call (texture_tables); the texel image of a call
   int tex_mode = 0; TexRec* tex_rec = nullptr; unsigned* tex_data = nullptr; float* tex_io = nullptr; size_t tex_io_floats = 0;
+  // lidar scans (mjh_scan / mjh_scan_device, scan.hip): the angle tables of the last call's pattern — the device buffer the kernel reads,
+  // the pinned host buffer the upload is issued from (scan_up marks the upload's end: the host buffer is not rewritten before it) —
+  // and the pattern they hold; a call with the same pattern uploads nothing
+  float* scan_tab = nullptr; size_t scan_tab_floats = 0; float* scan_host = nullptr; size_t scan_host_floats = 0; hipEvent_t scan_up = nullptr;
+  bool scan_have = false; int scan_w = 0, scan_h = 0; double scan_az[2] = {0, 0}, scan_el[2] = {0, 0}; bool scan_table = false; std::vector<double> scan_elev;
 };
 
 static int pad32(int n) { return ((n + 31) / 32) * 32; }
@@ -813,6 +819,9 @@ extern "C" void mjh_destroy(mjh_engine* e) {
   if (e->ray_io) (void)hipFree(e->ray_io);
   if (e->render_io) (void)hipFree(e->render_io);
   if (e->tex_io) (void)hipFree(e->tex_io);
+  if (e->scan_tab) (void)hipFree(e->scan_tab);
+  if (e->scan_host) (void)hipHostFree(e->scan_host);
+  if (e->scan_up) (void)hipEventDestroy(e->scan_up);
   if (e->h_dense) (void)hipHostFree(e->h_dense);
   if (e->h_wn) (void)hipHostFree(e->h_wn);
   if (e->h_io) (void)hipHostFree(e->h_io);
@@ -2143,6 +2152,98 @@ extern "C" int mjh_depth(mjh_engine* e, int env0, int n, const mjh_depth_options
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(depth, d_depth, nout * sizeof(float), hipMemcpyDeviceToHost, e->stream));
   if (geomid) HIPCHK(hipMemcpyAsync(geomid, d_gid, nout * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return MJH_OK;
+}
+
+// ---- lidar range images (mjh_scan / mjh_scan_device, scan.hip): the pattern's angle tables (dev_scan.h) on the engine's stream when the
+// pattern is not the last call's, ray_scene() (with the body poses when the sensor is a site), then mjh_scan_kernel on the same stream.
+extern "C" void mjh_scan_default_options(mjh_scan_options* o) {
+  if (!o) return;
+  o->site = -1; o->width = 360; o->height = 1;
+  o->azimuth0 = -3.14159265358979323846; o->azimuth_step = 2.0 * 3.14159265358979323846 / 360.0;
+  o->elevation = nullptr; o->elevation0 = 0.0; o->elevation_step = 0.0;
+  o->bodyexclude = -1; o->flg_static = 1; o->cull = 1; o->cutoff = 0.0;
+}
+// argument checks shared by both entry points: nothing is launched when one fails
+static int scan_check(const mjh_engine* e, int env0, int n, const mjh_scan_options& o, const void* range) {
+  const mjh_model* m = e->model;
+  if (o.site < -1 || o.site >= m->nsite) { mjh_set_error("mjh_scan: site id out of range"); return MJH_ERR_ARG; }
+  if (o.bodyexclude < -1 || o.bodyexclude >= m->nbody) { mjh_set_error("mjh_scan: bodyexclude out of range"); return MJH_ERR_ARG; }
+  if (env0 < 0 || n <= 0 || env0 + n > e->nenv) { mjh_set_error("mjh_scan: env range out of bounds"); return MJH_ERR_ARG; }
+  if (const char* bad = scan_pattern_error(o.width, o.height, n, o.azimuth0, o.azimuth_step, o.elevation, o.elevation0, o.elevation_step)) {
+    mjh_set_error(std::string("mjh_scan: ") + bad); return MJH_ERR_ARG;
+  }
+  if (!range) { mjh_set_error("mjh_scan: null pointer"); return MJH_ERR_ARG; }
+  return MJH_OK;
+}
+// the tables of the (checked) pattern in e->scan_tab: uploaded in stream order from the engine's pinned buffer unless they are there already
+static int scan_tables(mjh_engine* e, const mjh_scan_options& o) {
+  const bool table = o.elevation != nullptr;
+  bool same = e->scan_have && e->scan_w == o.width && e->scan_h == o.height && e->scan_az[0] == o.azimuth0 && e->scan_az[1] == o.azimuth_step && e->scan_table == table;
+  if (same && table) same = std::equal(e->scan_elev.begin(), e->scan_elev.end(), o.elevation);
+  if (same && !table) same = e->scan_el[0] == o.elevation0 && e->scan_el[1] == o.elevation_step;
+  if (same) return MJH_OK;
+  e->scan_have = false;
+  const size_t need = 2 * ((size_t)o.width + (size_t)o.height);
+  if (!e->scan_up) HIPCHK(hipEventCreateWithFlags(&e->scan_up, hipEventDisableTiming));
+  else HIPCHK(hipEventSynchronize(e->scan_up));      // (the last upload has read the host buffer)
+  if (need > e->scan_host_floats) {
+    if (e->scan_host) { HIPCHK(hipHostFree(e->scan_host)); e->scan_host = nullptr; e->scan_host_floats = 0; }
+    HIPCHK(hipHostMalloc((void**)&e->scan_host, need * sizeof(float), hipHostMallocDefault));
+    e->scan_host_floats = need;
+  }
+  int rc = io_reserve(e, &e->scan_tab, &e->scan_tab_floats, need);
+  if (rc) return rc;
+  scan_fill_tables(o.width, o.height, o.azimuth0, o.azimuth_step, o.elevation, o.elevation0, o.elevation_step, e->scan_host);
+  HIPCHK(hipMemcpyAsync(e->scan_tab, e->scan_host, need * sizeof(float), hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipEventRecord(e->scan_up, e->stream));
+  e->scan_w = o.width; e->scan_h = o.height; e->scan_az[0] = o.azimuth0; e->scan_az[1] = o.azimuth_step;
+  e->scan_table = table; e->scan_el[0] = o.elevation0; e->scan_el[1] = o.elevation_step;
+  if (table) e->scan_elev.assign(o.elevation, o.elevation + o.height); else e->scan_elev.clear();
+  e->scan_have = true;
+  return MJH_OK;
+}
+extern "C" int mjh_scan_device(mjh_engine* e, int env0, int n, const mjh_scan_options* opt, float* d_range, int* d_geomid, float* d_points) {
+  ENG(e);
+  mjh_scan_options o; mjh_scan_default_options(&o);
+  if (opt) o = *opt;
+  int rc = scan_check(e, env0, n, o, d_range);
+  if (rc) return rc;
+  rc = scan_tables(e, o);
+  if (rc) return rc;
+  const mjh_model* m = e->model;
+  ScanArgs A{};
+  rc = ray_scene(e, env0, n, o.site >= 0, o.bodyexclude, o.flg_static, o.cutoff, &A.W, &A.T);
+  if (rc) return rc;
+  A.range = d_range; A.geomid = d_geomid; A.points = d_points; A.tab = e->scan_tab;
+  A.width = o.width; A.height = o.height; A.tw_log = scan_tile_shape(o.height); A.cull = o.cull ? 1 : 0;
+  A.az_step = (float)std::fabs(o.azimuth_step);
+  if (!(A.az_step >= std::fabs(o.azimuth_step))) A.az_step = std::nextafter(A.az_step, INFINITY);      // (rounded up: the half-span test may only err towards `no cone`)
+  A.site_body = -1;
+  if (o.site >= 0) {
+    A.site_body = m->site_bodyid[o.site];
+    for (int k = 0; k < 3; k++) A.site_pos[k] = (float)m->site_pos[3 * o.site + k];
+    for (int k = 0; k < 4; k++) A.site_quat[k] = (float)m->site_quat[4 * o.site + k];
+  }
+  HIPCHK(mjh_launch_scan(e->stream, A));
+  return MJH_OK;
+}
+extern "C" int mjh_scan(mjh_engine* e, int env0, int n, const mjh_scan_options* opt, float* range, int* geomid, float* points) {
+  ENG(e);
+  mjh_scan_options o; mjh_scan_default_options(&o);
+  if (opt) o = *opt;
+  int rc = scan_check(e, env0, n, o, range);
+  if (rc) return rc;
+  const size_t nout = (size_t)n * o.width * o.height;
+  rc = ray_io_reserve(e, 5 * nout);
+  if (rc) return rc;
+  float* const d_range = e->ray_io; int* const d_gid = (int*)(e->ray_io + nout); float* const d_pts = e->ray_io + 2 * nout;
+  rc = mjh_scan_device(e, env0, n, &o, d_range, geomid ? d_gid : nullptr, points ? d_pts : nullptr);
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(range, d_range, nout * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+  if (geomid) HIPCHK(hipMemcpyAsync(geomid, d_gid, nout * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  if (points) HIPCHK(hipMemcpyAsync(points, d_pts, 3 * nout * sizeof(float), hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   return MJH_OK;
 }

@@ -401,6 +401,57 @@ class Engine:
         o = self._depth_options(camera, width, height, options)
         _chk(self.lib, self.lib.mjh_depth_device(self.h, env0, n, C.byref(o), C.c_void_p(d_depth), C.c_void_p(d_geomid)), "mjh_depth_device")
 
+    # ---- lidar range images (a site of the model, every env)
+    def _scan_options(self, site, width, height, azimuth, elevation, options):
+        """-> (mjh_scan_options, the array that backs its elevation table: to be kept alive over the call)"""
+        o = capi.ScanOptions()
+        self.lib.mjh_scan_default_options(C.byref(o))
+        if isinstance(site, str):
+            sid = self.lib.mjh_name2id(self.model.ptr, 3, site.encode())
+            if sid < 0:
+                raise ValueError(f"no site named {site!r}")
+            site = sid
+        o.site = -1 if site is None else int(site); o.width = int(width); o.height = int(height)
+        if azimuth is not None:
+            o.azimuth0, o.azimuth_step = float(azimuth[0]), float(azimuth[1])
+        table = None
+        if isinstance(elevation, tuple):
+            if len(elevation) != 2:
+                raise ValueError("elevation is (elevation0, elevation_step) or an array of `height` angles")
+            o.elevation0, o.elevation_step = float(elevation[0]), float(elevation[1])
+        elif elevation is not None:
+            table = np.ascontiguousarray(elevation, dtype=np.float64).reshape(-1)
+            if table.size != o.height:
+                raise ValueError("the elevation table needs `height` entries")
+            o.elevation = capi.dptr(table)
+        for k, v in options.items():
+            if k not in ("bodyexclude", "flg_static", "cull", "cutoff"):
+                raise TypeError(f"unknown scan option {k!r}")
+            setattr(o, k, v)
+        return o, table
+
+    def scan(self, site, width, height, azimuth=None, elevation=None, env0=0, n=None, points=False, **options):
+        """the lidar scan from site `site` (id or name; None / -1: the world frame) in envs [env0, env0 + n): `width` columns at azimuth
+        azimuth[0] + j azimuth[1] and `height` rows at elevation[0] + i elevation[1] (a tuple) or at the angles of an array, radians.
+        options: bodyexclude, flg_static, cull, cutoff (mjh_scan_options).
+        -> (range [n, height, width] float32, geomid [n, height, width] int32[, points [n, height, width, 3] float32 in the sensor
+        frame]); a miss is (-1, -1[, (0, 0, 0)])"""
+        n = self.nenv - env0 if n is None else n
+        o, table = self._scan_options(site, width, height, azimuth, elevation, options)
+        shape = (max(n, 0), max(o.height, 0), max(o.width, 0))
+        rng = np.zeros(shape, dtype=np.float32); gid = np.zeros(shape, dtype=np.int32)
+        pts = np.zeros(shape + (3,), dtype=np.float32) if points else None
+        _chk(self.lib, self.lib.mjh_scan(self.h, env0, n, C.byref(o), C.c_void_p(rng.ctypes.data), C.c_void_p(gid.ctypes.data),
+                                         C.c_void_p(pts.ctypes.data) if points else None), "mjh_scan")
+        return (rng, gid, pts) if points else (rng, gid)
+
+    def scan_device(self, d_range, d_geomid, d_points, site, width, height, azimuth=None, elevation=None, env0=0, n=None, **options):
+        """mjh_scan_device: device addresses (data_ptr()) of fp32 range and int32 geomid [n, height, width] and fp32 points
+        [n, height, width, 3] (d_geomid and d_points may be None); enqueued on the engine's stream, valid after synchronize()"""
+        n = self.nenv - env0 if n is None else n
+        o, table = self._scan_options(site, width, height, azimuth, elevation, options)
+        _chk(self.lib, self.lib.mjh_scan_device(self.h, env0, n, C.byref(o), C.c_void_p(d_range), C.c_void_p(d_geomid), C.c_void_p(d_points)), "mjh_scan_device")
+
     # ---- RGB-D images: depth, geom id, world-frame normal, shaded colour
     def _render_options(self, camera, width, height, options):
         o = capi.RenderOptions()
