@@ -649,6 +649,56 @@ int mjh_scan_device(mjh_engine*, int env0, int n, const mjh_scan_options*,
 /* host pointers (fp32; geomid and points may be NULL): calls the device form through the engine-owned staging buffer and synchronises */
 int mjh_scan(mjh_engine*, int env0, int n, const mjh_scan_options*, float* range, int* geomid, float* points);
 
+/* Height scans (elevation maps): a regular height x width grid of PARALLEL rays cast under a site of the model in every env — how high
+ * is the terrain under and around a mobile base, turned with its heading but not with its roll and pitch.  Cameras and lidars fan out
+ * from one origin; this projection is orthographic.  The rays are generated on the device from the grid and the site's pose in each
+ * env: no ray buffer is uploaded, and a sensor on a moving body follows it per env.
+ *   Sensor frame: the site's world pose in the env, origin o and rotation S; site = -1 is the world frame.
+ *   Grid frame G = (gx, gy, gz), chosen by `align`:
+ *     MJH_HSCAN_ALIGN_YAW (default): gz = (0, 0, 1) in the world; gx is the site's x axis projected onto the world's xy-plane and
+ *       normalised; gy = gz x gx.  If the squared length of the projection is below 1e-6 (the site's x axis within about 0.06 degrees
+ *       of vertical) gx is the world's x axis.  The rays point along the world's -z: roll and pitch of the carrier do not tilt the grid.
+ *     MJH_HSCAN_ALIGN_BASE: G = S; the rays point along the site's -z (an orthographic depth camera bolted to the body).
+ *     MJH_HSCAN_ALIGN_WORLD: G is the identity; the site supplies the translation only.
+ *   Cell (row i, column j) lies in the grid frame at x_j = offset[0] + (j - (width - 1) / 2) spacing[0] and y_i = offset[1] +
+ *   (i - (height - 1) / 2) spacing[1]: row 0 is the lowest y, column 0 the lowest x.  Its ray starts at o + gx x_j + gy y_i + gz above
+ *   and goes along -gz.
+ *   range: the Euclidean distance from the ray's start to the nearest visible surface; a miss is range -1, geomid -1.
+ *   points: (x_j, y_i, above - range) in the GRID frame: z is the terrain height relative to the sensor's origin.  A miss takes range 0
+ *   in that formula: it is the ray's start point (mjh_scan's rule: a miss is the origin of its beam).
+ *   Everything else is mjh_ray's on the same engine: the semantics per geom type (a start point inside a geom sees its far surface),
+ *   inactive slots, per-env geom sizes, mjh_ray_set_mesh_mode and mjh_ray_set_mesh_surface, the lower geom id on an exact fp32 tie,
+ *   cutoff (applied to range), flg_static, and the call-sequence rules (a pending mjh_step1 goes out first, a window hand-over is
+ *   dropped).  Nothing of state, statistics, warm start or time is written.
+ *   exclude_tree: 0 (default): bodyexclude hides that one body.  1: every geom whose body has the same body_rootid as bodyexclude is
+ *   hidden — the sensor's whole kinematic tree, base, wheels and arm.  The engine uploads the root-id table at the first call that asks.
+ *   cull: a wavefront casts a tile of 64 cells (1 x 64 for a single row, up to 8 x 8) and walks only the bounded geoms whose bounding
+ *   sphere touches the half-infinite cylinder around the tile's rays.  cull = 0 makes every tile visit every geom.  The two give the
+ *   same bits (the cull may never cost a hit).
+ * A site or body id out of range, exclude_tree = 1 with bodyexclude < 0, an unknown align, a non-positive size (or n * width * height of
+ * 2^30 or more), a spacing that is not finite or not > 0, an offset or `above` that is not finite, a cell coordinate that overflows
+ * fp32, an env range out of bounds or a NULL range pointer return MJH_ERR_ARG and launch nothing. */
+enum { MJH_HSCAN_ALIGN_YAW = 0, MJH_HSCAN_ALIGN_BASE = 1, MJH_HSCAN_ALIGN_WORLD = 2 };
+typedef struct mjh_heightscan_options {
+  int site;                 /* sensor frame; -1: the world frame */
+  int align;                /* MJH_HSCAN_ALIGN_* */
+  int width, height;        /* cells per row (along gx) and rows (along gy); n*width*height below 2^30 */
+  double spacing[2];        /* cell pitch along gx and gy, > 0 */
+  double offset[2];         /* the grid's centre in the grid frame */
+  double above;             /* the rays start this far along +gz */
+  int bodyexclude;          /* as mjh_ray_options */
+  int exclude_tree;         /* 1: hide every body of bodyexclude's kinematic tree */
+  int flg_static;           /* as mjh_ray_options */
+  int cull;                 /* 1 (default): tile culling; 0: every tile visits every geom -- same bits */
+  double cutoff;            /* > 0: a range beyond it is a miss */
+} mjh_heightscan_options;
+void mjh_heightscan_default_options(mjh_heightscan_options*);   /* -1, YAW, 16, 16, {0.1, 0.1}, {0, 0}, 1.0, -1, 0, 1, 1, 0 */
+/* device pointers; enqueued on the engine's stream, no synchronisation; d_geomid and d_points may be NULL.  options may be NULL */
+int mjh_heightscan_device(mjh_engine*, int env0, int n, const mjh_heightscan_options*,
+                          float* d_range /*[n][height][width]*/, int* d_geomid /*or NULL*/, float* d_points /*[n][height][width][3] or NULL*/);
+/* host pointers (fp32; geomid and points may be NULL): calls the device form through the engine-owned staging buffer and synchronises */
+int mjh_heightscan(mjh_engine*, int env0, int n, const mjh_heightscan_options*, float* range, int* geomid, float* points);
+
 /* RGB-D images: beside mjh_depth's depth and geom id, the world-frame surface normal at every pixel's hit and a shaded colour image.
  * Two launches on the engine's stream: the depth launch exactly as mjh_depth_device issues it (so depth and geomid are mjh_depth's
  * bits), then a shading kernel that reads those two images, regenerates each pixel's ray and resolves the normal on the one geom

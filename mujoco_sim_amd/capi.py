@@ -171,6 +171,11 @@ class ScanOptions(C.Structure):
                 ("elevation", c_double_p), ("elevation0", C.c_double), ("elevation_step", C.c_double), ("bodyexclude", C.c_int),
                 ("flg_static", C.c_int), ("cull", C.c_int), ("cutoff", C.c_double)]
 
+class HeightScanOptions(C.Structure):
+    _fields_ = [("site", C.c_int), ("align", C.c_int), ("width", C.c_int), ("height", C.c_int), ("spacing", C.c_double * 2),
+                ("offset", C.c_double * 2), ("above", C.c_double), ("bodyexclude", C.c_int), ("exclude_tree", C.c_int),
+                ("flg_static", C.c_int), ("cull", C.c_int), ("cutoff", C.c_double)]
+
 class LightOptions(C.Structure):
     _fields_ = [("shadows", C.c_int), ("cull", C.c_int), ("bias", C.c_float)]
 
@@ -290,6 +295,9 @@ SYMBOLS = [
     ("mjh_scan_default_options", None, [C.POINTER(ScanOptions)]),
     ("mjh_scan", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(ScanOptions), _vp, _vp, _vp]),
     ("mjh_scan_device", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(ScanOptions), _vp, _vp, _vp]),
+    ("mjh_heightscan_default_options", None, [C.POINTER(HeightScanOptions)]),
+    ("mjh_heightscan", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(HeightScanOptions), _vp, _vp, _vp]),
+    ("mjh_heightscan_device", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(HeightScanOptions), _vp, _vp, _vp]),
     ("mjh_render_default_options", None, [C.POINTER(RenderOptions)]),
     ("mjh_render", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(RenderOptions), _vp, _vp, _vp, _vp]),
     ("mjh_render_device", C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(RenderOptions), _vp, _vp, _vp, _vp]),

@@ -18,6 +18,7 @@
 #include "dev_ray.h"
 #include "dev_depth.h"
 #include "dev_scan.h"
+#include "dev_heightscan.h"
 #include "dev_render.h"
 #include "dev_light.h"
 #include "dev_texture.h"
@@ -143,6 +144,9 @@ struct mjh_engine {
   // and the pattern they hold; a call with the same pattern uploads nothing
   float* scan_tab = nullptr; size_t scan_tab_floats = 0; float* scan_host = nullptr; size_t scan_host_floats = 0; hipEvent_t scan_up = nullptr;
   bool scan_have = false; int scan_w = 0, scan_h = 0; double scan_az[2] = {0, 0}, scan_el[2] = {0, 0}; bool scan_table = false; std::vector<double> scan_elev;
+  // height scans (mjh_heightscan / mjh_heightscan_device, heightscan.hip): the model's body_rootid on the device, uploaded at the first call
+  // with exclude_tree = 1 (an engine that never asks has no such buffer)
+  int* hscan_root = nullptr;
 };
 
 static int pad32(int n) { return ((n + 31) / 32) * 32; }
@@ -822,6 +826,7 @@ extern "C" void mjh_destroy(mjh_engine* e) {
   if (e->scan_tab) (void)hipFree(e->scan_tab);
   if (e->scan_host) (void)hipHostFree(e->scan_host);
   if (e->scan_up) (void)hipEventDestroy(e->scan_up);
+  if (e->hscan_root) (void)hipFree(e->hscan_root);
   if (e->h_dense) (void)hipHostFree(e->h_dense);
   if (e->h_wn) (void)hipHostFree(e->h_wn);
   if (e->h_io) (void)hipHostFree(e->h_io);
@@ -2240,6 +2245,72 @@ extern "C" int mjh_scan(mjh_engine* e, int env0, int n, const mjh_scan_options* 
   if (rc) return rc;
   float* const d_range = e->ray_io; int* const d_gid = (int*)(e->ray_io + nout); float* const d_pts = e->ray_io + 2 * nout;
   rc = mjh_scan_device(e, env0, n, &o, d_range, geomid ? d_gid : nullptr, points ? d_pts : nullptr);
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(range, d_range, nout * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+  if (geomid) HIPCHK(hipMemcpyAsync(geomid, d_gid, nout * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  if (points) HIPCHK(hipMemcpyAsync(points, d_pts, 3 * nout * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return MJH_OK;
+}
+
+// ---- height scans (mjh_heightscan / mjh_heightscan_device, heightscan.hip): the checks (dev_heightscan.h), the root-id table at the first
+// call with exclude_tree = 1, ray_scene() (with the body poses when the sensor is a site), then mjh_heightscan_kernel on the same stream.
+extern "C" void mjh_heightscan_default_options(mjh_heightscan_options* o) {
+  if (!o) return;
+  o->site = -1; o->align = MJH_HSCAN_ALIGN_YAW; o->width = 16; o->height = 16;
+  o->spacing[0] = 0.1; o->spacing[1] = 0.1; o->offset[0] = 0.0; o->offset[1] = 0.0; o->above = 1.0;
+  o->bodyexclude = -1; o->exclude_tree = 0; o->flg_static = 1; o->cull = 1; o->cutoff = 0.0;
+}
+// argument checks shared by both entry points: nothing is launched when one fails
+static int hscan_check(const mjh_engine* e, int env0, int n, const mjh_heightscan_options& o, const void* range) {
+  if (const char* bad = hscan_args_error(e->model->nsite, e->model->nbody, e->nenv, env0, n, o, range)) {
+    mjh_set_error(std::string("mjh_heightscan: ") + bad); return MJH_ERR_ARG;
+  }
+  return MJH_OK;
+}
+extern "C" int mjh_heightscan_device(mjh_engine* e, int env0, int n, const mjh_heightscan_options* opt, float* d_range, int* d_geomid, float* d_points) {
+  ENG(e);
+  mjh_heightscan_options o; mjh_heightscan_default_options(&o);
+  if (opt) o = *opt;
+  int rc = hscan_check(e, env0, n, o, d_range);
+  if (rc) return rc;
+  const mjh_model* m = e->model;
+  if (o.exclude_tree && !e->hscan_root) {
+    int* root = nullptr;
+    HIPCHK(hipMalloc((void**)&root, (size_t)m->nbody * sizeof(int)));
+    const hipError_t filled = hipMemcpy(root, m->body_rootid, (size_t)m->nbody * sizeof(int), hipMemcpyHostToDevice);
+    if (filled != hipSuccess) (void)hipFree(root);
+    HIPCHK(filled);
+    e->hscan_root = root;      // (only a table that was filled is kept)
+  }
+  HScanArgs A{};
+  rc = ray_scene(e, env0, n, o.site >= 0, o.bodyexclude, o.flg_static, o.cutoff, &A.W, &A.T);
+  if (rc) return rc;
+  A.range = d_range; A.geomid = d_geomid; A.points = d_points;
+  A.width = o.width; A.height = o.height; A.tw_log = scan_tile_shape(o.height); A.cull = o.cull ? 1 : 0; A.align = o.align;
+  A.ox = (float)o.offset[0]; A.oy = (float)o.offset[1]; A.hx = (float)(0.5 * o.spacing[0]); A.hy = (float)(0.5 * o.spacing[1]);
+  A.above = (float)o.above;
+  A.rootid = o.exclude_tree ? e->hscan_root : nullptr; A.root_ex = o.exclude_tree ? m->body_rootid[o.bodyexclude] : -1;
+  A.site_body = -1;
+  if (o.site >= 0) {
+    A.site_body = m->site_bodyid[o.site];
+    for (int k = 0; k < 3; k++) A.site_pos[k] = (float)m->site_pos[3 * o.site + k];
+    for (int k = 0; k < 4; k++) A.site_quat[k] = (float)m->site_quat[4 * o.site + k];
+  }
+  HIPCHK(mjh_launch_heightscan(e->stream, A));
+  return MJH_OK;
+}
+extern "C" int mjh_heightscan(mjh_engine* e, int env0, int n, const mjh_heightscan_options* opt, float* range, int* geomid, float* points) {
+  ENG(e);
+  mjh_heightscan_options o; mjh_heightscan_default_options(&o);
+  if (opt) o = *opt;
+  int rc = hscan_check(e, env0, n, o, range);
+  if (rc) return rc;
+  const size_t nout = (size_t)n * o.width * o.height;
+  rc = ray_io_reserve(e, 5 * nout);
+  if (rc) return rc;
+  float* const d_range = e->ray_io; int* const d_gid = (int*)(e->ray_io + nout); float* const d_pts = e->ray_io + 2 * nout;
+  rc = mjh_heightscan_device(e, env0, n, &o, d_range, geomid ? d_gid : nullptr, points ? d_pts : nullptr);
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(range, d_range, nout * sizeof(float), hipMemcpyDeviceToHost, e->stream));
   if (geomid) HIPCHK(hipMemcpyAsync(geomid, d_gid, nout * sizeof(int), hipMemcpyDeviceToHost, e->stream));

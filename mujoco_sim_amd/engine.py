@@ -452,6 +452,56 @@ class Engine:
         o, table = self._scan_options(site, width, height, azimuth, elevation, options)
         _chk(self.lib, self.lib.mjh_scan_device(self.h, env0, n, C.byref(o), C.c_void_p(d_range), C.c_void_p(d_geomid), C.c_void_p(d_points)), "mjh_scan_device")
 
+    # ---- height scans (a grid of parallel rays under a site of the model, every env)
+    _HSCAN_ALIGN = {"yaw": 0, "base": 1, "world": 2}
+
+    def _heightscan_options(self, site, width, height, spacing, offset, above, align, options):
+        o = capi.HeightScanOptions()
+        self.lib.mjh_heightscan_default_options(C.byref(o))
+        if isinstance(site, str):
+            sid = self.lib.mjh_name2id(self.model.ptr, 3, site.encode())
+            if sid < 0:
+                raise ValueError(f"no site named {site!r}")
+            site = sid
+        if align not in self._HSCAN_ALIGN:
+            raise ValueError('align is "yaw", "base" or "world"')
+        spacing = (spacing, spacing) if np.isscalar(spacing) else tuple(spacing)
+        if len(spacing) != 2 or len(offset) != 2:
+            raise ValueError("spacing and offset are (x, y) pairs")
+        o.site = -1 if site is None else int(site); o.align = self._HSCAN_ALIGN[align]; o.width = int(width); o.height = int(height)
+        o.spacing[0], o.spacing[1] = float(spacing[0]), float(spacing[1])
+        o.offset[0], o.offset[1] = float(offset[0]), float(offset[1])
+        o.above = float(above)
+        for k, v in options.items():
+            if k not in ("bodyexclude", "exclude_tree", "flg_static", "cull", "cutoff"):
+                raise TypeError(f"unknown height-scan option {k!r}")
+            setattr(o, k, v)
+        return o
+
+    def height_scan(self, site, width, height, spacing, offset=(0, 0), above=1.0, align="yaw", env0=0, n=None, points=False, **options):
+        """the height scan under site `site` (id or name; None / -1: the world frame) in envs [env0, env0 + n): a `height` x `width` grid
+        of parallel rays, cell (i, j) at offset + ((j, i) - ((width, height) - 1) / 2) * spacing in the grid frame, cast from `above`
+        along the grid's -z.  align: "yaw" (the grid follows the site's heading, the rays go along the world's -z), "base" (the
+        site's own frame) or "world".  spacing: (x, y) or one number.  options: bodyexclude, exclude_tree, flg_static, cull, cutoff
+        (mjh_heightscan_options).
+        -> (range [n, height, width] float32, geomid [n, height, width] int32[, points [n, height, width, 3] float32 in the grid
+        frame: (x, y, above - range)]); a miss is (-1, -1[, the ray's start point])"""
+        n = self.nenv - env0 if n is None else n
+        o = self._heightscan_options(site, width, height, spacing, offset, above, align, options)
+        shape = (max(n, 0), max(o.height, 0), max(o.width, 0))
+        rng = np.zeros(shape, dtype=np.float32); gid = np.zeros(shape, dtype=np.int32)
+        pts = np.zeros(shape + (3,), dtype=np.float32) if points else None
+        _chk(self.lib, self.lib.mjh_heightscan(self.h, env0, n, C.byref(o), C.c_void_p(rng.ctypes.data), C.c_void_p(gid.ctypes.data),
+                                               C.c_void_p(pts.ctypes.data) if points else None), "mjh_heightscan")
+        return (rng, gid, pts) if points else (rng, gid)
+
+    def height_scan_device(self, d_range, d_geomid, d_points, site, width, height, spacing, offset=(0, 0), above=1.0, align="yaw", env0=0, n=None, **options):
+        """mjh_heightscan_device: device addresses (data_ptr()) of fp32 range and int32 geomid [n, height, width] and fp32 points
+        [n, height, width, 3] (d_geomid and d_points may be None); enqueued on the engine's stream, valid after synchronize()"""
+        n = self.nenv - env0 if n is None else n
+        o = self._heightscan_options(site, width, height, spacing, offset, above, align, options)
+        _chk(self.lib, self.lib.mjh_heightscan_device(self.h, env0, n, C.byref(o), C.c_void_p(d_range), C.c_void_p(d_geomid), C.c_void_p(d_points)), "mjh_heightscan_device")
+
     # ---- RGB-D images: depth, geom id, world-frame normal, shaded colour
     def _render_options(self, camera, width, height, options):
         o = capi.RenderOptions()
