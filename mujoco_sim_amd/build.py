@@ -14,7 +14,7 @@ LIB = os.path.join(HERE, "libmjhip.so")
 API = os.path.join("..", "..", "include", "mjhip.h")
 KERNEL_HEADERS = ["step_kernel.h", "patch_pgs.h", "window_pgs.h", "dev_math.h", "dev_collide.h", "dev_convex.h", "dev_types.h"]
 DENSE_HEADERS = ["dense_pgs.h"] + KERNEL_HEADERS
-WINDOW_HEADERS = ["window_kernel.h", "step_kernel.h", "patch_pgs.h", "window_pgs.h", "dev_math.h", "dev_collide.h", "dev_convex.h", "dev_types.h"]
+WINDOW_HEADERS = ["window_kernel.h", "window_tiles.h", "step_kernel.h", "patch_pgs.h", "window_pgs.h", "dev_math.h", "dev_collide.h", "dev_convex.h", "dev_types.h"]
 # source -> headers it includes (besides itself)
 SOURCES = {
     "engine.hip": KERNEL_HEADERS + ["dev_ray.h", "ray_bvh.h", "dev_depth.h", "dev_scan.h", "dev_heightscan.h", "dev_render.h", "dev_light.h", "dev_texture.h", "ray_tables.h", API],
@@ -37,7 +37,9 @@ SOURCES = {
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-fno-slp-vectorize", "-Wno-unused-result"]
 # per-source flags.  window.hip: its window forms are written as fully unrolled loops over register-resident windows; past clang's default
 # budget for `#pragma unroll` (16 k instructions) a window loop stays a loop and its operand arrays land in scratch memory
-SOURCE_FLAGS = {"window.hip": ["-mllvm", "-pragma-unroll-threshold=200000"]}
+# ... and its tile builds run on the matrix cores (window_tiles.h) with their accumulators in architectural registers: with accumulation registers
+# as MFMA operands the register allocator keeps 9 more registers in the lean instance and 18 more copies in its six-window sweep loop
+SOURCE_FLAGS = {"window.hip": ["-mllvm", "-pragma-unroll-threshold=200000", "-mllvm", "-amdgpu-mfma-vgpr-form"]}
 FLAGS += os.environ.get("MJH_EXTRA_FLAGS", "").split()      # A/B builds (e.g. -DPP_NRC=0 -DMJH_STEP_WAVES=3), together with MJH_BUILD_DIR / MJHIP_LIB
 if os.environ.get("MJH_BUILD_DIR"):
     OBJ = os.environ["MJH_BUILD_DIR"]; LIB = os.path.join(OBJ, "libmjhip.so")

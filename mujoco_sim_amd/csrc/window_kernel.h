@@ -3,6 +3,7 @@
 // for the step kernel's instances), launched from engine.hip through mjh_launch_window.
 #pragma once
 #include "step_kernel.h"
+#include "window_tiles.h"
 
 #ifdef WN_PROF_CLK
 #define WN_STAT0(x) min((int)(((long long)__builtin_amdgcn_s_memtime() - wn_t0) >> 5) + 1, (1 << 22) - 1)       // (probe build: the wave's clocks where the contact count goes; the launch order keeps its own hint)
@@ -358,19 +359,9 @@ DEV void wn_run32(const DConst* __restrict__ C, const DState& S, const int env0,
     wn_load_row<NV>(rows + (2 * w + hq) * WN_NK * 16, ok, W.J, W.aref, W.R);
     float acc[16], acx[16], Jx[NV];
 #pragma unroll
-    for (int sidx = 0; sidx < 16; sidx++) { acc[sidx] = 0.0f; acx[sidx] = 0.0f; }
-#pragma unroll
     for (int k = 0; k < NV; k++) Jx[k] = WN_SWZ16(W.J[k]);   // the other half's row q: upper lanes see the lower rows
-#pragma unroll
-    for (int k = 0; k < NV; k++) asm volatile("" : "+v"(W.J[k]), "+v"(Jx[k]));
-    asm volatile("s_nop 1");
-    // (dof k outermost, the 16 tile entries inside: consecutive multiply-adds go to DIFFERENT accumulators.  Entry after entry the compiler put an
-    //  `s_nop` between every two of them — its hazard model counts the accumulator of a DPP multiply-add as a DPP source of the next one — and a lone
-    //  wave pays an issue slot for each: half of the tile build's slots.  Every accumulator still sums its dofs in the same order: bitwise.)
-#define WN_ACC(sidx) PP_FMAC_BC(acc[sidx], W.J[k], W.J[k], sidx); PP_FMAC_BC(acx[sidx], Jx[k], W.J[k], sidx);
-#pragma unroll
-    for (int k = 0; k < NV; k++) { PP_BC16(WN_ACC) }
-#undef WN_ACC
+    // (window_tiles.h: the sixteen entries of the own half's tile and of the cross tile, each the sum of its dofs in k order)
+    wn_tile16<NV>(W.J, W.J, acc); wn_tile16<NV>(Jx, W.J, acx);
     float diag = 0.0f;
 #pragma unroll
     for (int k = 0; k < NV; k++) diag += W.J[k] * W.J[k];
@@ -620,21 +611,13 @@ template <int N64W, int N64T> DEV void wn_run64(const DConst* __restrict__ C, co
     const float inv = ARqq < MJ_MINVAL ? 0.0f : 1.0f / ARqq, ninv = -inv;
     W.nw = ninv; W.half = 0.5f * ARqq;
     // tile row: acc_r = J^_lane . J^_r for the 64 rows r of the window.  The rows of 16-lane group G come over through the LDS crossbar
-    // (ds_bpermute: lane (G, q) to every group's lane q), then sixteen broadcast multiply-add chains as in the 16-row form
+    // (ds_bpermute: lane (G, q) to every group's lane q), then the sixteen dot products as in the 16-row form (window_tiles.h)
 #pragma unroll
     for (int G = 0; G < 4; G++) {
       float Jg[NV], acc[16];
 #pragma unroll
       for (int k = 0; k < NV; k++) Jg[k] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((16 * G + q) << 2, __builtin_bit_cast(int, W.J[k])));
-#pragma unroll
-      for (int sidx = 0; sidx < 16; sidx++) acc[sidx] = 0.0f;
-#pragma unroll
-      for (int k = 0; k < NV; k++) asm volatile("" : "+v"(W.J[k]), "+v"(Jg[k]));
-      asm volatile("s_nop 1");
-#define WN_ACC(sidx) PP_FMAC_BC(acc[sidx], Jg[k], W.J[k], sidx);
-#pragma unroll
-      for (int k = 0; k < NV; k++) { PP_BC16(WN_ACC) }
-#undef WN_ACC
+      wn_tile16<NV>(Jg, W.J, acc);
 #pragma unroll
       for (int sidx = 0; sidx < 16; sidx++) W.A[16 * G + sidx] = (16 * G + sidx) < lane ? ninv * acc[sidx] : 0.0f;
     }
@@ -665,15 +648,7 @@ template <int N64W, int N64T> DEV void wn_run64(const DConst* __restrict__ C, co
       float Jg[NV], acc[16];
 #pragma unroll
       for (int k = 0; k < NV; k++) Jg[k] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((16 * G + q) << 2, __builtin_bit_cast(int, TL.J[k])));
-#pragma unroll
-      for (int sidx = 0; sidx < 16; sidx++) acc[sidx] = 0.0f;
-#pragma unroll
-      for (int k = 0; k < NV; k++) asm volatile("" : "+v"(TL.J[k]), "+v"(Jg[k]));
-      asm volatile("s_nop 1");
-#define WN_ACC(sidx) PP_FMAC_BC(acc[sidx], Jg[k], TL.J[k], sidx);
-#pragma unroll
-      for (int k = 0; k < NV; k++) { PP_BC16(WN_ACC) }
-#undef WN_ACC
+      wn_tile16<NV>(Jg, TL.J, acc);
 #pragma unroll
       for (int c4 = 0; c4 < 4; c4++) {
         const int r0 = 16 * G + 4 * c4;
@@ -867,18 +842,10 @@ __global__ __launch_bounds__(64, 1) void mjh_window_kernel(const DConst* __restr
     wn_load_row<NV>(rows + w * WN_NK * 16, ok, W.J, W.aref, W.R);
   };
   // tile row of a window: acc_r = J^_q . J^_r for the 16 rows r of the window (every lane of the row at once), then -AR_qr / AR_qq, r < q
-  auto make_tile = [&](WnWin<NV>& W) __attribute__((always_inline)) {
-    float acc[16];
-#pragma unroll
-    for (int s = 0; s < 16; s++) acc[s] = 0.0f;
-#pragma unroll
-    for (int k = 0; k < NV; k++) asm volatile("" : "+v"(W.J[k]));     // (materialised before the DPP reads below: no VALU write within two instructions of them)
-    asm volatile("s_nop 1");
-    // (dof k outermost: consecutive multiply-adds go to different accumulators, no `s_nop` between them — see wn_run32's tile build)
-#define WN_ACC(s) PP_FMAC_BC(acc[s], W.J[k], W.J[k], s);
-#pragma unroll
-    for (int k = 0; k < NV; k++) { PP_BC16(WN_ACC) }
-#undef WN_ACC
+  // (the sixteen dot products: window_tiles.h — on the matrix cores in the 24-slot instances, bit for bit the broadcast multiply-add loop the
+  //  32-slot instance keeps: its 475 registers leave no room for accumulators beside the windows)
+  constexpr bool TILE_MMA = WN_TILE_MFMA && NV == 24;
+  auto finish_tile = [&](WnWin<NV>& W, const float (&acc)[16]) __attribute__((always_inline)) {
     float diag = 0.0f;
 #pragma unroll
     for (int k = 0; k < NV; k++) diag += W.J[k] * W.J[k];
@@ -889,6 +856,11 @@ __global__ __launch_bounds__(64, 1) void mjh_window_kernel(const DConst* __restr
     W.A1 = make_float4(4 < q ? ninv * acc[4] : 0.0f, 5 < q ? ninv * acc[5] : 0.0f, 6 < q ? ninv * acc[6] : 0.0f, 7 < q ? ninv * acc[7] : 0.0f);
     W.A2 = make_float4(8 < q ? ninv * acc[8] : 0.0f, 9 < q ? ninv * acc[9] : 0.0f, 10 < q ? ninv * acc[10] : 0.0f, 11 < q ? ninv * acc[11] : 0.0f);
     W.A3 = make_float4(12 < q ? ninv * acc[12] : 0.0f, 13 < q ? ninv * acc[13] : 0.0f, 14 < q ? ninv * acc[14] : 0.0f, 0.0f);
+  };
+  auto make_tile = [&](WnWin<NV>& W) __attribute__((always_inline)) {
+    float acc[16];
+    wn_tile16<NV, TILE_MMA>(W.J, W.J, acc);
+    finish_tile(W, acc);
   };
   // windows beyond the register-resident ones: the whole record — the
   // next NL windows of every env in LDS (the kernel has no other use for it: 40 KB per wave at four waves per CU), the rest in the env's
@@ -916,39 +888,39 @@ __global__ __launch_bounds__(64, 1) void mjh_window_kernel(const DConst* __restr
   float4* const xl = (float4*)wn_lds + (rho * nl * NX4) * 16 + q;                                   // LDS tier: window NW + j at xl + j * NX4 * 16
   float4* const xg = (float4*)(wb + WN_ROWS + M.win_maxw * WN_NK * 16) + q;                         // global tier: window w at xg + w * NX4 * 16
   const int nwl = min(nwmax, NW + nl);
-#pragma unroll
-  for (int w = 0; w < NW; w++) if (w < nwmax) { load_rows(win[w], w); make_tile(win[w]); }
   // The register-resident windows are swept two at a time: window 2j + 1 takes its residual from the acceleration BEFORE window 2j's
   // deltas plus the cross tile X_j[r] = (-1 / AR_qq) J^_{2j+1,q} . J^_{2j,r} times those deltas (16 broadcast multiply-adds), so that both
   // windows' J^T delta go through ONE transpose-reduce: ~255 instead of 300 issue slots per 32 rows on every env's chain.  Same rows, same
   // order, same row math; the grouping of the arithmetic differs (fp32 rounding).
   static_assert(NW % 2 == 0, "register-resident windows are swept in pairs");
   float4 X[NW / 2][4];
-  auto make_cross = [&](WnWin<NV>& A, WnWin<NV>& B, float4 (&Xo)[4]) __attribute__((always_inline)) {
-    float acx[16];
-#pragma unroll
-    for (int sidx = 0; sidx < 16; sidx++) acx[sidx] = 0.0f;
-#pragma unroll
-    for (int k = 0; k < NV; k++) asm volatile("" : "+v"(A.J[k]), "+v"(B.J[k]));
-    asm volatile("s_nop 1");
-#define WN_ACX(sidx) PP_FMAC_BC(acx[sidx], A.J[k], B.J[k], sidx);
-#pragma unroll
-    for (int k = 0; k < NV; k++) { PP_BC16(WN_ACX) }
-#undef WN_ACX
+  auto finish_cross = [&](const WnWin<NV>& B, const float (&acx)[16], float4 (&Xo)[4]) __attribute__((always_inline)) {
     Xo[0] = make_float4(B.nw * acx[0], B.nw * acx[1], B.nw * acx[2], B.nw * acx[3]);
     Xo[1] = make_float4(B.nw * acx[4], B.nw * acx[5], B.nw * acx[6], B.nw * acx[7]);
     Xo[2] = make_float4(B.nw * acx[8], B.nw * acx[9], B.nw * acx[10], B.nw * acx[11]);
     Xo[3] = make_float4(B.nw * acx[12], B.nw * acx[13], B.nw * acx[14], B.nw * acx[15]);
   };
+  auto make_cross = [&](WnWin<NV>& A, WnWin<NV>& B, float4 (&Xo)[4]) __attribute__((always_inline)) {
+    float acx[16];
+    wn_tile16<NV, TILE_MMA>(A.J, B.J, acx);
+    finish_cross(B, acx, Xo);
+  };
   constexpr bool X_LDS = XL && NV == 24 && WN_FILL && WN_X_LDS;
   float4* const xs = (float4*)wn_lds + (4 * nl * NX4) * 16 + lane;                              // (behind the tier) pair j, quarter c of the lane at xs[(4 j + c) * 64]
 #pragma unroll
-  for (int j = 0; j < NW / 2; j++) if (2 * j + 1 < nwmax) {
-    make_cross(win[2 * j], win[2 * j + 1], X[j]);
-    if constexpr (X_LDS) {
+  for (int j = 0; j < NW / 2; j++) {
+    // a pair's two tiles and its cross tile: three independent chains on the matrix cores, issued interleaved
+    if (2 * j + 1 < nwmax) {
+      WnWin<NV>& A = win[2 * j]; WnWin<NV>& B = win[2 * j + 1];
+      load_rows(A, 2 * j); load_rows(B, 2 * j + 1);
+      float acca[16], accb[16], acx[16];
+      wn_tile16_pair<NV, TILE_MMA>(A.J, B.J, acca, accb, acx);
+      finish_tile(A, acca); finish_tile(B, accb); finish_cross(B, acx, X[j]);
+      if constexpr (X_LDS) {
 #pragma unroll
-      for (int c = 0; c < 4; c++) xs[(4 * j + c) * 64] = X[j][c];
-    }
+        for (int c = 0; c < 4; c++) xs[(4 * j + c) * 64] = X[j][c];
+      }
+    } else if (2 * j < nwmax) { load_rows(win[2 * j], 2 * j); make_tile(win[2 * j]); }
   }
   for (int w = NW; w < nwl; w++) { WnWin<NV> W; load_rows(W, w); make_tile(W); store_ext(xl + (w - NW) * NX4 * 16, W, 0.0f); }
   for (int w = nwl; w < nwmax; w++) { WnWin<NV> W; load_rows(W, w); make_tile(W); if (mine) store_ext(xg + w * NX4 * 16, W, 0.0f); }
