@@ -808,7 +808,9 @@ const float* mjh_mirror_field(const mjh_mirror*, int which, int* row_width);
 /* the mirrored simulation time of the n environments in fp64 (field MJH_MIRROR_TIME holds the same doubles: row_width 2 floats) */
 const double* mjh_mirror_time(const mjh_mirror*);
 
-/* debug: mean shader-clock ticks from kernel start to each of the 16 stage boundaries of one fused step */
+/* debug: mean shader-clock ticks from kernel start to each of the 16 stage boundaries of one fused step
+   (with_inverse bit 3, window-chain models: of the assemble-only launch alone; a -DMJH_COLLIDE_PROBE library also fills out[16 .. 18],
+   so callers of that form pass 20 doubles) */
 int mjh_debug_stage_cycles(mjh_engine*, int with_inverse, double* out16);
 /* debug: raw stamps of one step launch, out[nenv*20] indexed by launch position: [0..15] shader-clock stage stamps,
  * [16],[17] 100 MHz wall clock at start/end, [18] HW_ID | XCC_ID<<32, [19] env id (tools/timeline.py) */

@@ -55,7 +55,11 @@ struct DModel {
 };
 
 // per-env state in HBM (fp32, env-major rows)
+#ifdef MJH_COLLIDE_PROBE
+#define PROF_STRIDE 24   // (probe build: [20 .. 22] three stamps inside the collision stage)
+#else
 #define PROF_STRIDE 20   // x_prof: 16 stage stamps (shader clock), [16],[17] wall clock start/end, [18] HW_ID|XCC_ID<<32
+#endif
 struct DState {
   float *qpos, *qvel, *qacc, *qacc_ws, *qvel_ref, *qfrc_applied, *ddq, *dq, *qfrc_inverse;
   double* time;  // [nenv] simulation time in fp64 (d->time is mjtNum: ROS stamps, the 10 kHz gate and the RTF logic read it)

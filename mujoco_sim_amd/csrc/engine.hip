@@ -198,13 +198,16 @@ static int window_tier(const mjh_engine* e) {
   return nl_env >= 0 ? nl_env : ((tier || e->M.win_maxw > 16) ? nl_full : 0);
 }
 // wmode (window chain of small free-body models): 0 the whole step; 1 the assemble launch only, every env handed over — the split API's
-// mjh_step1 [+ mjh_inverse] doing the work mjh_step2 would otherwise repeat (the rows only exist in LDS); 2 the window kernel only
+// mjh_step1 [+ mjh_inverse] doing the work mjh_step2 would otherwise repeat (the rows only exist in LDS); 2 the window kernel only;
+// 3 the contact snapshot (mjh_get_contacts) through the assemble-only instance — the collision code the model's steps run —, nothing handed over
 static int launch_on(mjh_engine* e, hipStream_t st, int env0, int n, int nsteps, int ph, int xflags, int wmode = 0, int tier_nl = -1) {
   if (n <= 0) return MJH_OK;
   // window sweep (window_pgs.h): every launch that runs mj_step2 to the end (the fused step and the split API's step2) of a small
   // free-body model = assemble launch (PH_PRE), then four envs per wavefront through the sweeps and the integration
-  const bool window = e->M.window && e->S.wbuf && (ph & PH_STEP2) && !(ph & (PH_NOINT | PH_PRE | PH_POST)) && !(xflags & ~(XF_FORCE | XF_DEFER));
-  if (window) ph |= PH_PRE;
+  // (wmode 1 may carry XF_PROF: mjh_debug_stage_cycles stamps the assemble-only instance; no window launch follows it)
+  const bool snap = wmode == 3 && e->M.window && e->S.wbuf && ph == 0 && xflags == (XF_CON | XF_NOSTORE);
+  const bool window = snap || (e->M.window && e->S.wbuf && (ph & PH_STEP2) && !(ph & (PH_NOINT | PH_PRE | PH_POST)) && !(xflags & ~(XF_FORCE | XF_DEFER | (wmode == 1 ? XF_PROF : 0))));
+  if (window && !snap) ph |= PH_PRE;
   if (wmode && !window) { mjh_set_error("internal: window-chain launch mode on a launch that is not one"); return MJH_ERR_STATE; }
   if (wmode == 1) xflags |= XF_DEFER;
   if (wmode != 2) {
@@ -234,7 +237,7 @@ static int launch_on(mjh_engine* e, hipStream_t st, int env0, int n, int nsteps,
 #undef MJH_LAUNCH
   HIPCHK(hipGetLastError());
   }
-  if (window && wmode != 1) {
+  if (window && wmode != 1 && wmode != 3) {
     // LDS tier: windows beyond the register-resident ones, as many as leave four waves per CU (40 KB per wave)
     const int nl = tier_nl >= 0 ? tier_nl : window_tier(e);
     const size_t lds = (size_t)4 * nl * WN_XREC(e->M.win_nvt) * 16 * sizeof(float);
@@ -1448,7 +1451,7 @@ extern "C" int mjh_get_contacts(mjh_engine* e, int env, double* dist, double* po
     // and the launch ends there (XF_NOSTORE): state, statistics, time and warm start of the env are not touched
     StateGuard guard(&e->S);
     e->S.x_contacts = e->scratch;
-    rc = launch(e, env, 1, 1, 0, XF_CON | XF_NOSTORE);
+    rc = launch(e, env, 1, 1, 0, XF_CON | XF_NOSTORE, (e->M.window && e->S.wbuf) ? 3 : 0);
   }
   if (rc) return rc;
   std::vector<float> tmp((size_t)mc * CON_STRIDE + 4);
@@ -1803,6 +1806,9 @@ extern "C" int mjh_debug_stage_cycles(mjh_engine* e, int with_inverse, double* o
         HIPCHK(hipGetLastError());
         rc = launch(e, 0, e->nenv, 1, PH_STEP2 | PH_POST, (with_inverse & 4) ? XF_PROF : 0);
       }
+    } else if ((with_inverse & 8) && e->M.window && e->S.wbuf) {
+      // the window chain's assemble-only instance alone, every env handed over (no window launch: the guard puts the state back)
+      rc = launch(e, 0, e->nenv, 1, ph, XF_PROF, 1);
     } else
     rc = launch(e, 0, e->nenv, 1, ph, XF_PROF);
   }
@@ -1812,6 +1818,14 @@ extern "C" int mjh_debug_stage_cycles(mjh_engine* e, int with_inverse, double* o
   for (int k = 0; k < 16; k++) out[k] = 0;
   for (int en = 0; en < e->nenv; en++) for (int k = 0; k < 16; k++) { long long v = h[(size_t)en*PROF_STRIDE+k]; out[k] += v ? (double)(v - h[(size_t)en*PROF_STRIDE]) : 0.0; }
   for (int k = 0; k < 16; k++) out[k] /= e->nenv;
+#ifdef MJH_COLLIDE_PROBE
+  // probe build: out[16 .. 18] the three stamps inside the collision stage (the caller passes 20 doubles)
+  for (int k = 0; k < 3; k++) {
+    out[16 + k] = 0;
+    for (int en = 0; en < e->nenv; en++) { long long v = h[(size_t)en*PROF_STRIDE+20+k]; out[16 + k] += v ? (double)(v - h[(size_t)en*PROF_STRIDE]) : 0.0; }
+    out[16 + k] /= e->nenv;
+  }
+#endif
   return MJH_OK;
 }
 

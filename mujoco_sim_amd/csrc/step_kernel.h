@@ -36,6 +36,13 @@
 #define ASM_PROBE_BEGIN() do {} while (0)
 #define ASM_PROBE_STORE() do {} while (0)
 #endif
+// Probe build (-DMJH_COLLIDE_PROBE, never the default library): three more stamps inside the collision stage — behind the per-lane narrow
+// phase, behind the scan of the counts, behind the emit — in x_prof[20 .. 22] (tools/collide_stage_profile.py prices the box-box lanes and the emit)
+#ifdef MJH_COLLIDE_PROBE
+#define CPROF(k) do { if ((xflags & XF_PROF) && lane == 0) S.x_prof[(size_t)blockIdx.x * PROF_STRIDE + 20 + (k)] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
+#else
+#define CPROF(k) do {} while (0)
+#endif
 #define MINIMP 0.0001f
 #define MAXIMP 0.9999f
 
@@ -998,6 +1005,12 @@ __global__ __launch_bounds__(64, MJH_STEP_WAVES_T) void mjh_step_kernel(const DC
 #ifndef MJH_LAZY_LDS
 #define MJH_LAZY_LDS (WPRE != 0)
 #endif
+  // collision of the window chain's assemble-only instances (plain and HF): the contact emit with lanes = contacts (collide_round).
+  // -DMJH_COLLIDE_LANES=0: the per-pair loop (A/B builds).  Every other instance keeps the per-pair loop and its code
+#ifndef MJH_COLLIDE_LANES
+#define MJH_COLLIDE_LANES 1
+#endif
+  constexpr bool COLLIDE_LANES = MJH_COLLIDE_LANES != 0 && WPRE != 0;
 #define LA(n) const XArr<MJH_LAZY_LDS, &Lay::n> s_##n(lds, L);
   MJH_LDS_SMALL(LA)
 #undef LA
@@ -1475,9 +1488,44 @@ step_again:      // (a backward goto instead of a `for`: the instances without t
           }
           WSYNC();      // (the prism lanes wrote the pairs' staging; each owner lane reads its own below)
         }
+        CPROF(0);
         const int incl = wave_incl_scan_i(n, lane);
         const int total = wave_last_i(incl);
         const int first = conbase + incl - n;
+        CPROF(1);
+        if constexpr (COLLIDE_LANES) {
+          // emit with lanes = contacts, 64 at a time: contact c of the round belongs to the first pair lane whose inclusive count exceeds c
+          // (binary search over the scanned counts by ds_bpermute), is record c - (that lane's exclusive count) of its staging, and lands
+          // in slot conbase + c — the per-pair loop's order and values
+          // (the pair lane's exclusive count and staging offset travel as one word: counts of a round stay below 2^10 — 64 pairs of 8)
+          const int exst = (incl - n) | ((int)(st - s_stage) << 10);
+          const int gw = g1 | (g2 << 12) | (max(geom_condim[g1], geom_condim[g2]) << 24);
+          const float mg = margin - gap;
+          WSYNC();
+          for (int c0 = 0; c0 < total; c0 += 64) {
+            // (lanes beyond the round's last contact repeat it and store nothing: every lane stays active for the ds_bpermute reads)
+            const int c = min(c0 + lane, total - 1), idx = conbase + c;
+            const bool live = c0 + lane < total && idx < M.maxcon;
+            int pl = 0;
+#pragma unroll
+            for (int stp = 32; stp > 0; stp >>= 1) { if (__builtin_amdgcn_ds_bpermute((pl + stp - 1) << 2, incl) <= c) pl += stp; }
+            const int es = __builtin_amdgcn_ds_bpermute(pl << 2, exst);
+            const float* r = s_stage + (es >> 10) + (c - (es & 1023)) * RAW_STRIDE;
+            float* cc = s_con + min(idx, M.maxcon - 1) * CON_STRIDE;
+            float fr[9]; fr[0] = r[4]; fr[1] = r[5]; fr[2] = r[6];
+            const float r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3];
+            if (live) { cc[0] = r0; cc[1] = r1; cc[2] = r2; cc[3] = r3; }
+            make_frame(fr);
+            if (live) {
+#pragma unroll
+              for (int k = 0; k < 9; k++) cc[4+k] = fr[k];
+            }
+            const int gwp = __builtin_amdgcn_ds_bpermute(pl << 2, gw);
+            if (live) cc[CON_GEOMS] = __int_as_float(gwp);
+            const int mgp = __builtin_amdgcn_ds_bpermute(pl << 2, __builtin_bit_cast(int, mg));
+            if (live) cc[CON_MARGIN] = __int_as_float(mgp);
+          }
+        } else
         for (int q = 0; q < n; q++) {
           const int idx = first + q;
           if (idx >= M.maxcon) break;
@@ -1490,6 +1538,7 @@ step_again:      // (a backward goto instead of a `for`: the instances without t
           for (int k = 0; k < 9; k++) c[4+k] = fr[k];
           c[CON_GEOMS] = __int_as_float(g1 | (g2 << 12) | (max(geom_condim[g1], geom_condim[g2]) << 24)); c[CON_MARGIN] = margin - gap;
         }
+        CPROF(2);
         conbase += total;
       };
       // bounding-sphere / plane-distance cull of one pair (the narrow phase repeats it; it is cheap)
