@@ -853,6 +853,42 @@ void mjh_set_layout_policy(int policy);
  * contact-patch sweep (same order, same iterates up to fp32 rounding).  mjh_window_solver() reports what an engine runs. */
 void mjh_set_window_solver(int on);
 int mjh_window_solver(const mjh_engine*);
+
+/* ---- contact report: which bodies touch what, and with how much force, for every env, on the device.
+ * mjh_set_contact_report(on): engines created afterwards (process-wide; default 0, environment MJH_CONTACT_REPORT).  Off is the engine as
+ * it is without this section: the same layouts, kernel instances, launches and bits.  On, every launch that takes the solve to its end
+ * (mjh_step, mjh_step2, mjh_forward) leaves per env, in fp32, the report of its LAST solve (as sensordata):
+ *   ncon; one record of 20 words per contact of the collision stage, in its order — dist, pos[3], frame[9], force[4], geom1, geom2, dim
+ *   (three ints) —; cfrc_ext[6 * nbody].
+ *   force: normal, tangent 1, tangent 2, torque about the normal, in the contact frame, ON geom2's body (mj_contactForce for condim <= 4;
+ *   condim 6 does not exist here).  A contact that got no constraint rows (row capacity) is listed with zero force.
+ *   cfrc_ext: d->cfrc_ext — torque(3) then force(3) per body, world axes, about the subtree COM of the body's tree root; body 0 is zero;
+ *   it sums xfrc_applied, the contact forces and the connect / weld forces.
+ * The price: such an engine lays its model out as a model with a force sensor — everything the report reads stays alive after the solve,
+ * no diagonal-M form, no contact-patch sweep, no window chain, the many-body layout steps in one fused launch (DESIGN.md section 4h has the
+ * figures).  Results agree with a report-off engine to fp32 rounding, as with every layout choice.
+ * Every function below returns MJH_ERR_STATE on an engine created with the report off.  Before the first solve, and for an env after
+ * mjh_reset, the report is ncon = 0 and zeros.  Not forwarded by mjh_group, not part of the pinned mirror. */
+void mjh_set_contact_report(int on);
+int mjh_contact_report(const mjh_engine*);   /* what this engine does; NULL: the switch, i.e. what an engine created now would do */
+/* the engine's device buffers: int ncon[nenv], float records[nenv][maxcon][20], float cfrc_ext[nenv][6 * nbody]; valid until mjh_destroy,
+ * they hold the report of the last solve once the engine's stream has reached it.  Any output may be NULL. */
+int mjh_contact_report_device(mjh_engine*, const void** d_ncon, const void** d_records, const void** d_cfrc_ext, int* maxcon);
+/* host copies (synchronise): ncon [n]; per env maxcon slots of dist [1], pos [3], frame [9], force [6] (mj_contactForce's layout: entries 4
+ * and 5 are zero), geom [2], dim [1]; slots from ncon on are zero.  Any output may be NULL. */
+int mjh_get_contact_forces(mjh_engine*, int env0, int n, int* ncon, double* dist, double* pos, double* frame, double* force, int* geom, int* dim);
+int mjh_get_cfrc_ext(mjh_engine*, int env0, int n, double* cfrc_ext /* [n * 6 * nbody] */);
+/* Net contact force ON selected bodies, world axes: force[i][s] = sum over env env0 + i's contacts that touch body[s] (+ the record's force
+ * where the body carries geom2, - where it carries geom1), restricted to contacts whose other body is against[s] unless that is -1
+ * (against NULL: all -1); count[i][s] = contacts that entered the sum.  One launch of mjh_contact_force_kernel (csrc/contact.hip) on the
+ * engine's stream behind the steps queued so far; the selection table is uploaded only when it differs from the last call's.  The order
+ * of the additions is fixed per env and body: a sum does not depend on nenv, env0, n or the other selected bodies (bitwise).
+ * A contact between two selected bodies enters both sums with opposite signs.  Device form: d_force float [n][nsel][3], d_count int
+ * [n][nsel] or NULL, no synchronisation.  Host form: doubles, synchronises; count may be NULL.
+ * An env range out of bounds, nsel <= 0, a body id outside [0, nbody), an `against` outside [-1, nbody) or a NULL force pointer return
+ * MJH_ERR_ARG and launch nothing; a contact capacity beyond 3276 (the kernel's LDS stage) MJH_ERR_CAPACITY. */
+int mjh_body_contact_force_device(mjh_engine*, int env0, int n, int nsel, const int* body, const int* against, void* d_force, void* d_count);
+int mjh_body_contact_force(mjh_engine*, int env0, int n, int nsel, const int* body, const int* against, double* force, int* count);
 int mjh_set_cohorts(mjh_engine*, int n);
 int mjh_get_cohorts(const mjh_engine*);
 /* mjh_step(e, n) of an articulated model in the LDS-resident layout runs up to `n` steps per launch and cohort with the environment's

@@ -326,6 +326,13 @@ SYMBOLS = [
     ("mjh_set_layout_policy", None, [C.c_int]),
     ("mjh_set_window_solver", None, [C.c_int]),
     ("mjh_window_solver", C.c_int, [_vp]),
+    ("mjh_set_contact_report", None, [C.c_int]),
+    ("mjh_contact_report", C.c_int, [_vp]),
+    ("mjh_contact_report_device", C.c_int, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), c_int_p]),
+    ("mjh_get_contact_forces", C.c_int, [_vp, C.c_int, C.c_int, c_int_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p]),
+    ("mjh_get_cfrc_ext", C.c_int, [_vp, C.c_int, C.c_int, c_double_p]),
+    ("mjh_body_contact_force_device", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, c_int_p, c_int_p, _vp, _vp]),
+    ("mjh_body_contact_force", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, c_int_p, c_int_p, c_double_p, c_int_p]),
     ("mjh_set_pgs_row_order", None, [C.c_int]),
     ("mjh_set_cohorts", C.c_int, [_vp, C.c_int]),
     ("mjh_get_cohorts", C.c_int, [_vp]),

@@ -124,7 +124,18 @@ struct DHField { int has_hfield, o_hfield_nrow, o_hfield_ncol, o_hfield_adr, o_h
 // schedule nor own slots for bv / phi (they lie in the contact records, as in instance 2), and its base-row pool starts at float J instead of L.J
 struct DWpre { int slim, J; };
 
-struct DConst { DModel M; Lay L; DHField H; DWpre W; };
+// contact report (mjh_set_contact_report; behind W for the same reason, and in this device-resident descriptor, not in DState: no kernel
+// argument moves).  Read by the articulated EXTRA instances of the step kernel only.  Per env: ncon [1], one record of CREP_STRIDE words per
+// contact in s_con order [maxcon] — dist, pos3, frame9, force4 (normal, tangent 1, tangent 2, torque about the normal: contact frame, on
+// geom2's body), geom1, geom2, dim (ints) —, and cfrc_ext [6 nbody] (torque3, force3 about the tree root's subtree COM, world axes)
+#define CREP_STRIDE 20
+#define CREP_FORCE 13
+#define CREP_GEOM1 17
+#define CREP_GEOM2 18
+#define CREP_DIM 19
+struct DReport { int on, maxcon; int* ncon; float* rec; float* cfrc; };
+
+struct DConst { DModel M; Lay L; DHField H; DWpre W; DReport R; };
 
 // kernel phases
 enum { PH_STEP1 = 1, PH_INV = 2, PH_STEP2 = 4, PH_NOINT = 8, PH_FKONLY = 16, PH_MULM = 32, PH_RESET = 64,

@@ -19,6 +19,7 @@
 #include "dev_depth.h"
 #include "dev_scan.h"
 #include "dev_heightscan.h"
+#include "dev_contact.h"
 #include "dev_render.h"
 #include "dev_light.h"
 #include "dev_texture.h"
@@ -73,6 +74,10 @@ struct mjh_engine {
   Lay L{};
   int lds_bytes = 0, lds_bytes_pre = 0;   // dynamic LDS per env of the step kernel; ... of its assemble-only instance (no patch pool: more envs per CU; HostPack's lds_bytes_wpre)
   DHField H{};                            // height fields (H.has_hfield: every launch of the step kernel takes an HF instance, hfield.hip)
+  bool report = false; DReport R{};       // contact report (mjh_set_contact_report when the engine was created): the kernels' descriptor of its buffers
+  // per-body contact force (mjh_body_contact_force_device, contact.hip): the selection table of the last call on the device — the pinned host
+  // buffer the upload is issued from, the event that marks the upload's end — and the selection it holds; a call with the same one uploads nothing
+  int2* csel_tab = nullptr; int2* csel_host = nullptr; int csel_cap = 0; hipEvent_t csel_up = nullptr; std::vector<int> csel_have; float* csel_io = nullptr; size_t csel_io_words = 0;
   DWpre W{};                              // patch models: where the assemble-only instance keeps its base rows and per-base vectors (derive_device_model)
   size_t dense_lds = 0, dense_solve_lds = 0;   // dynamic LDS of mjh_dense_build_kernel / mjh_dense_solve_kernel
   // dense solver on / off per cohort: mjh_order_kernel leaves "an env of the cohort swept long" in a host-mapped word (four slots per
@@ -213,13 +218,13 @@ static int launch_on(mjh_engine* e, hipStream_t st, int env0, int n, int nsteps,
   if (wmode != 2) {
 #define MJH_LAUNCH2(NR, DG, CX) do { if (e->H.has_hfield) HIPCHK(mjh_launch_step_hf(st, NR, DG, 0, n, (size_t)e->lds_bytes, e->dC, e->S, env0, nsteps, ph, xflags)); \
                                    else hipLaunchKernelGGL((mjh_step_kernel<NR, DG, CX>), dim3(n), dim3(64), (size_t)e->lds_bytes, st, e->dC, e->S, env0, nsteps, ph, xflags); } while (0)
-#define MJH_LAUNCH(NR, DG) do { if (extra_instance(e->M) || e->S.xfrc_applied) MJH_LAUNCH2(NR, DG, true); else MJH_LAUNCH2(NR, DG, false); } while (0)
+#define MJH_LAUNCH(NR, DG) do { if (extra_instance(e->M) || e->S.xfrc_applied || e->report) MJH_LAUNCH2(NR, DG, true); else MJH_LAUNCH2(NR, DG, false); } while (0)
   const int nr = e->M.big ? 8 : (e->M.nv <= 16 ? 1 : (e->M.nv <= 32 ? 2 : 4));   // 8: many-body layout, running acceleration in LDS
   static const bool slim = !(getenv("MJH_WINDOW_SLIM") && atoi(getenv("MJH_WINDOW_SLIM")) == 0);
   if (window && slim) {
     // the assemble-only instance (WPRE): the step kernel without any sweep of its own — 116 - 119 VGPRs (allocated: 120) instead of 236, so that
     // its waves fit beside the lean window kernel's on a SIMD (376 + 120 <= 512 registers: tests/test_window_register_budget.py)
-    const bool cx = extra_instance(e->M) || e->S.xfrc_applied;
+    const bool cx = extra_instance(e->M) || e->S.xfrc_applied || e->report;
     static const bool slim_lds = !(getenv("MJH_WINDOW_SLIM_LDS") && atoi(getenv("MJH_WINDOW_SLIM_LDS")) == 0);
     static const int wpad = getenv("MJH_WPRE_LDS_PAD") ? std::max(0, atoi(getenv("MJH_WPRE_LDS_PAD"))) : 0;      // (occupancy experiments: bytes of unused LDS per assemble-only workgroup)
     const size_t wlds = (size_t)((slim_lds && e->lds_bytes_pre > 0) ? e->lds_bytes_pre : e->lds_bytes) + (size_t)wpad;
@@ -297,15 +302,22 @@ static int pair_cap(int t1, int t2) {
 
 // Host-only derivation of the device model: packed tables, derived topology tables, capacities and the LDS
 // layout.  Needs no HIP device (mjh_query_lds_bytes uses it for capacity planning and in the CPU tests).
-struct HostPack { DModel M{}; Lay L{}; DHField H{}; DWpre W{}; std::vector<int> I; std::vector<float> F; int o_controlled = 0, o_odom = 0, lds_bytes = 0, lds_bytes_pre = 0, lds_bytes_wpre = 0; long long gstride = 0; };      // lds_bytes_pre: an assemble-only launch's extent in the fused layout's own offsets; lds_bytes_wpre: what that launch allocates
+struct HostPack { DModel M{}; Lay L{}; DHField H{}; DWpre W{}; bool report = false; std::vector<int> I; std::vector<float> F; int o_controlled = 0, o_odom = 0, lds_bytes = 0, lds_bytes_pre = 0, lds_bytes_wpre = 0; long long gstride = 0; };      // lds_bytes_pre: an assemble-only launch's extent in the fused layout's own offsets; lds_bytes_wpre: what that launch allocates
 // Gauss-Seidel order of engines created afterwards (mjhip.h): 1 = mj_solPGS's own row order
 #define MJH_WINDOW_MAXCON 128    // contact capacity up to which a small free-body model steps through the window chain
 static int g_window_solver = getenv("MJH_WINDOW") ? (atoi(getenv("MJH_WINDOW")) != 0) : 1;
 extern "C" void mjh_set_window_solver(int on) { g_window_solver = on ? 1 : 0; }
 static int g_pgs_row_order = 1;
+// Contact report of engines created afterwards (mjhip.h): the step kernel leaves the contacts with their solver forces and cfrc_ext per env.
+// Such an engine lays its model out as it would a model with a force sensor (the report reads the position stage, the contact records and the
+// block forces after the solve): no diagonal-M form, no patch sweep, no window chain, one fused launch per step in the many-body layout
+static int g_contact_report = getenv("MJH_CONTACT_REPORT") ? (atoi(getenv("MJH_CONTACT_REPORT")) != 0) : 0;
+extern "C" void mjh_set_contact_report(int on) { g_contact_report = on ? 1 : 0; }
 extern "C" void mjh_set_pgs_row_order(int mode) { g_pgs_row_order = mode < 0 || mode > 2 ? 1 : mode; }
 static void derive_device_model(const mjh_model* m, HostPack& hp, bool force_big = false, bool allow_patch = true) {
   DModel& M = hp.M; std::vector<int>& I = hp.I; std::vector<float>& F = hp.F;
+  const bool report = g_contact_report != 0;
+  hp.report = report;
   // ---- derived integer tables
   const int nb = m->nbody, nv = m->nv, nj = m->njnt, ng = m->ngeom;
   std::vector<int> subtreesize(nb, 1), lastdof(nb, -1), stageadr(m->npair, 0), fl_dof, gc_body, controlled(std::max(nv, 1), 0), odom(10, -1);
@@ -338,7 +350,7 @@ static void derive_device_model(const mjh_model* m, HostPack& hp, bool force_big
   }
   rowW = ((rowW + 3) / 4) * 4;
   // every tree a single free body about its own COM with principal axes = body axes  =>  M is diagonal
-  bool diagM = m->ntree > 0 && m->neq == 0 && m->nsensor == 0 && m->nmocap == 0;   // (also implies: no limit / equality rows, every block is a contact)
+  bool diagM = m->ntree > 0 && m->neq == 0 && m->nsensor == 0 && m->nmocap == 0 && !report;   // (also implies: no limit / equality rows, every block is a contact)
   for (int t = 0; t < m->ntree && diagM; t++) {
     const int b = m->tree_bodyid[t];
     diagM = m->tree_dofnum[t] == 6 && m->body_jntnum[b] == 1 && m->jnt_type[m->body_jntadr[b]] == MJH_JNT_FREE && subtreesize[b] == 1 &&
@@ -435,7 +447,8 @@ static void derive_device_model(const mjh_model* m, HostPack& hp, bool force_big
     M.big = big;
     // models with sensors read the position-stage arrays, the contact records and the velocity-stage vectors again AFTER the
     // solver (mj_sensorAcc): nothing of those is aliased then
-    const bool keep = m->nsensor > 0;
+    // ... and so does the contact report
+    const bool keep = m->nsensor > 0 || report;
     auto gput = [&](long long n) { long long o = goff; goff += ((std::max<long long>(n, 1) + 3) / 4) * 4; return (int)(-1 - o); };
     const int nblkcap = std::max(M.maxblk, 1);   // exact: the block builder never creates more than maxblk blocks
     // J / B pools: one row per non-contact block (equality, friction loss, limits), four interleaved rows per contact
@@ -571,9 +584,9 @@ static void derive_device_model(const mjh_model* m, HostPack& hp, bool force_big
       }
     } else L.zero = put(4);
     L.site = m->nsite > 0 ? put(12 * m->nsite) : 0;        // world frame of every site: pos(3) + rotation(9)
-    L.fext = m->nsensor > 0 ? put(6 * nb) : 0;             // external spatial force per body (mj_rnePostConstraint)
+    L.fext = (m->nsensor > 0 || report) ? put(6 * nb) : 0;   // external spatial force per body (mj_rnePostConstraint; cfrc_ext of the contact report)
     // (the site frames / external forces sit behind the patch pool: an assemble-only launch of a model that has them gets the whole layout)
-    if (m->nsite > 0 || m->nsensor > 0) { hp.lds_bytes_pre = off * (int)sizeof(float); wpre_floats = 0; }
+    if (m->nsite > 0 || m->nsensor > 0 || report) { hp.lds_bytes_pre = off * (int)sizeof(float); wpre_floats = 0; }
     hp.lds_bytes_wpre = wpre_floats ? wpre_floats * (int)sizeof(float) : hp.lds_bytes_pre;
     if (big) {   // hand-over vectors of the three-launch step (non-negative offsets into the scratch slice)
       auto graw = [&](int n) { long long o = goff; goff += ((std::max(n, 1) + 3) / 4) * 4; return (int)o; };
@@ -680,7 +693,7 @@ extern "C" int mjh_create(const mjh_model* m, int nenv, int device, void* stream
   e->model = m; e->nenv = nenv; e->device = device; e->stream = (hipStream_t)stream;
 
   HostPack hp; derive_fitting(m, hp);
-  e->M = hp.M; e->L = hp.L; e->H = hp.H; e->W = hp.W; e->lds_bytes = hp.lds_bytes; e->lds_bytes_pre = hp.lds_bytes_wpre; e->o_controlled = hp.o_controlled; e->o_odom = hp.o_odom;
+  e->M = hp.M; e->L = hp.L; e->H = hp.H; e->W = hp.W; e->report = hp.report; e->lds_bytes = hp.lds_bytes; e->lds_bytes_pre = hp.lds_bytes_wpre; e->o_controlled = hp.o_controlled; e->o_odom = hp.o_odom;
   DModel& M = e->M; std::vector<int>& I = hp.I; std::vector<float>& F = hp.F;
   e->hI = I;
   if (dev_alloc(e, &e->dI, I.size(), false) || dev_alloc(e, &e->dF, F.size(), false)) { mjh_destroy(e); return MJH_ERR_NO_DEVICE; }
@@ -689,8 +702,13 @@ extern "C" int mjh_create(const mjh_model* m, int nenv, int device, void* stream
   HIPCHK(hipStreamSynchronize(e->stream));
   M.I = e->dI; M.F = e->dF;
 
+  if (e->report) {   // contact report: zeros until the first solve
+    DReport& R = e->R;
+    R.on = 1; R.maxcon = e->M.maxcon; e->split3 = false;      // (the report reads the position stage after the solve: one fused launch)
+    if (dev_alloc(e, &R.ncon, (size_t)nenv) || dev_alloc(e, &R.rec, (size_t)nenv * R.maxcon * CREP_STRIDE) || dev_alloc(e, &R.cfrc, (size_t)nenv * 6 * e->M.nbody)) { mjh_destroy(e); return MJH_ERR_NO_DEVICE; }
+  }
   {
-    DConst hc; hc.M = e->M; hc.L = e->L; hc.H = e->H; hc.W = e->W;
+    DConst hc; hc.M = e->M; hc.L = e->L; hc.H = e->H; hc.W = e->W; hc.R = e->R;
     if (dev_alloc(e, &e->dC, 1, false)) { mjh_destroy(e); return MJH_ERR_NO_DEVICE; }
     HIPCHK(hipMemcpyAsync(e->dC, &hc, sizeof hc, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
@@ -830,6 +848,10 @@ extern "C" void mjh_destroy(mjh_engine* e) {
   if (e->scan_host) (void)hipHostFree(e->scan_host);
   if (e->scan_up) (void)hipEventDestroy(e->scan_up);
   if (e->hscan_root) (void)hipFree(e->hscan_root);
+  if (e->csel_tab) (void)hipFree(e->csel_tab);
+  if (e->csel_host) (void)hipHostFree(e->csel_host);
+  if (e->csel_up) (void)hipEventDestroy(e->csel_up);
+  if (e->csel_io) (void)hipFree(e->csel_io);
   if (e->h_dense) (void)hipHostFree(e->h_dense);
   if (e->h_wn) (void)hipHostFree(e->h_wn);
   if (e->h_io) (void)hipHostFree(e->h_io);
@@ -2266,6 +2288,126 @@ extern "C" int mjh_scan(mjh_engine* e, int env0, int n, const mjh_scan_options* 
   HIPCHK(hipStreamSynchronize(e->stream));
   return MJH_OK;
 }
+
+// ---- contact report (mjh_set_contact_report): the readers of what the step kernel's report stage left (step_kernel.h), and the per-body
+// contact force (contact.hip) on the same stream.
+static_assert(CF_REC_WORDS == CREP_STRIDE && CF_FORCE == CREP_FORCE && CF_GEOM1 == CREP_GEOM1 && CF_GEOM2 == CREP_GEOM2, "contact.hip reads the step kernel's record");
+extern "C" int mjh_contact_report(const mjh_engine* e) { return e ? (e->report ? 1 : 0) : g_contact_report; }      // (NULL: the switch itself)
+#define REPORT_ON(e, who) if (!(e)->report) { mjh_set_error(std::string(who) + ": the engine was created with the contact report off (mjh_set_contact_report)"); return MJH_ERR_STATE; }
+extern "C" int mjh_contact_report_device(mjh_engine* e, const void** d_ncon, const void** d_records, const void** d_cfrc_ext, int* maxcon) {
+  ENG_NOJOIN(e); KEEP_HANDOVER(e);
+  REPORT_ON(e, "mjh_contact_report_device");
+  if (d_ncon) *d_ncon = e->R.ncon;
+  if (d_records) *d_records = e->R.rec;
+  if (d_cfrc_ext) *d_cfrc_ext = e->R.cfrc;
+  if (maxcon) *maxcon = e->R.maxcon;
+  return MJH_OK;
+}
+extern "C" int mjh_get_contact_forces(mjh_engine* e, int env0, int n, int* ncon, double* dist, double* pos, double* frame, double* force, int* geom, int* dim) {
+  ENG(e); KEEP_HANDOVER(e);
+  REPORT_ON(e, "mjh_get_contact_forces");
+  RANGE(e, env0, n);
+  if (n == 0) return MJH_OK;
+  const int mc = e->R.maxcon;
+  std::vector<int> nc((size_t)n);
+  std::vector<float> rec((size_t)n * mc * CREP_STRIDE);
+  HIPCHK(hipMemcpyAsync(nc.data(), e->R.ncon + env0, nc.size() * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(rec.data(), e->R.rec + (size_t)env0 * mc * CREP_STRIDE, rec.size() * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  for (int i = 0; i < n; i++) {
+    const int k = std::max(0, std::min(nc[i], mc));
+    if (ncon) ncon[i] = k;
+    for (int c = 0; c < mc; c++) {
+      const size_t o = (size_t)i * mc + c;
+      const float* r = rec.data() + o * CREP_STRIDE;
+      const bool live = c < k;
+      if (dist) dist[o] = live ? r[0] : 0.0;
+      if (pos) for (int q = 0; q < 3; q++) pos[3*o+q] = live ? r[1+q] : 0.0;
+      if (frame) for (int q = 0; q < 9; q++) frame[9*o+q] = live ? r[4+q] : 0.0;
+      if (force) for (int q = 0; q < 6; q++) force[6*o+q] = (live && q < 4) ? r[CREP_FORCE+q] : 0.0;
+      int g[3] = {0, 0, 0};
+      if (live) std::memcpy(g, r + CREP_GEOM1, sizeof g);
+      if (geom) { geom[2*o] = g[0]; geom[2*o+1] = g[1]; }
+      if (dim) dim[o] = g[2];
+    }
+  }
+  return MJH_OK;
+}
+extern "C" int mjh_get_cfrc_ext(mjh_engine* e, int env0, int n, double* cfrc_ext) {
+  ENG(e); KEEP_HANDOVER(e);
+  REPORT_ON(e, "mjh_get_cfrc_ext");
+  RANGE(e, env0, n);
+  if (!cfrc_ext) return MJH_ERR_ARG;
+  const int w = 6 * e->M.nbody;
+  return get_rows(e, e->R.cfrc, w, w, env0, n, cfrc_ext);
+}
+// argument checks shared by both entry points: nothing is launched when one fails
+static int body_force_check(const mjh_engine* e, int env0, int n, int nsel, const int* body, const int* against, const void* force) {
+  if (env0 < 0 || n <= 0 || env0 + n > e->nenv) { mjh_set_error("mjh_body_contact_force: env range out of bounds"); return MJH_ERR_ARG; }
+  if (nsel <= 0 || !body || !force) { mjh_set_error("mjh_body_contact_force: empty selection or null pointer"); return MJH_ERR_ARG; }
+  if ((long long)n * nsel >= (1ll << 30)) { mjh_set_error("mjh_body_contact_force: n * nsel too large"); return MJH_ERR_ARG; }
+  for (int s = 0; s < nsel; s++) {
+    if (body[s] < 0 || body[s] >= e->M.nbody) { mjh_set_error("mjh_body_contact_force: body id out of range"); return MJH_ERR_ARG; }
+    if (against && (against[s] < -1 || against[s] >= e->M.nbody)) { mjh_set_error("mjh_body_contact_force: `against` out of range"); return MJH_ERR_ARG; }
+  }
+  if ((size_t)e->R.maxcon * CF_STAGE * sizeof(float) > 64 * 1024) { mjh_set_error("mjh_body_contact_force: contact capacity beyond the kernel's LDS stage"); return MJH_ERR_CAPACITY; }
+  return MJH_OK;
+}
+// the (checked) selection in e->csel_tab: uploaded in stream order from the engine's pinned buffer unless it is there already
+static int body_force_table(mjh_engine* e, int nsel, const int* body, const int* against) {
+  std::vector<int> want((size_t)2 * nsel);
+  for (int s = 0; s < nsel; s++) { want[2*s] = body[s]; want[2*s+1] = against ? against[s] : -1; }
+  if (e->csel_tab && want == e->csel_have) return MJH_OK;
+  e->csel_have.clear();
+  if (!e->csel_up) HIPCHK(hipEventCreateWithFlags(&e->csel_up, hipEventDisableTiming));
+  else HIPCHK(hipEventSynchronize(e->csel_up));      // (the last upload has read the host buffer)
+  if (nsel > e->csel_cap) {
+    if (e->csel_host) { HIPCHK(hipHostFree(e->csel_host)); e->csel_host = nullptr; }
+    if (e->csel_tab) { HIPCHK(hipStreamSynchronize(e->stream)); HIPCHK(hipFree(e->csel_tab)); e->csel_tab = nullptr; }
+    e->csel_cap = 0;
+    HIPCHK(hipHostMalloc((void**)&e->csel_host, (size_t)nsel * sizeof(int2), hipHostMallocDefault));
+    HIPCHK(hipMalloc((void**)&e->csel_tab, (size_t)nsel * sizeof(int2)));
+    e->csel_cap = nsel;
+  }
+  std::memcpy(e->csel_host, want.data(), want.size() * sizeof(int));
+  HIPCHK(hipMemcpyAsync(e->csel_tab, e->csel_host, (size_t)nsel * sizeof(int2), hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipEventRecord(e->csel_up, e->stream));
+  e->csel_have = want;
+  return MJH_OK;
+}
+extern "C" int mjh_body_contact_force_device(mjh_engine* e, int env0, int n, int nsel, const int* body, const int* against, void* d_force, void* d_count) {
+  ENG(e); KEEP_HANDOVER(e);
+  REPORT_ON(e, "mjh_body_contact_force_device");
+  int rc = body_force_check(e, env0, n, nsel, body, against, d_force);
+  if (rc) return rc;
+  rc = body_force_table(e, nsel, body, against);
+  if (rc) return rc;
+  ContactForceArgs A{};
+  A.ncon = e->R.ncon; A.rec = e->R.rec; A.geom_bodyid = e->dI + e->M.o_geom_bodyid; A.sel = e->csel_tab;
+  A.force = (float*)d_force; A.count = (int*)d_count;
+  A.env0 = env0; A.n = n; A.nsel = nsel; A.maxcon = e->R.maxcon; A.ngeom = e->M.ngeom;
+  HIPCHK(mjh_launch_contact_force(e->stream, A));
+  return MJH_OK;
+}
+extern "C" int mjh_body_contact_force(mjh_engine* e, int env0, int n, int nsel, const int* body, const int* against, double* force, int* count) {
+  ENG(e); KEEP_HANDOVER(e);
+  REPORT_ON(e, "mjh_body_contact_force");
+  int rc = body_force_check(e, env0, n, nsel, body, against, force);
+  if (rc) return rc;
+  const size_t nout = (size_t)n * nsel;
+  rc = io_reserve(e, &e->csel_io, &e->csel_io_words, 4 * nout);
+  if (rc) return rc;
+  float* const d_f = e->csel_io; int* const d_c = (int*)(e->csel_io + 3 * nout);
+  rc = mjh_body_contact_force_device(e, env0, n, nsel, body, against, d_f, d_c);
+  if (rc) return rc;
+  std::vector<float> f(3 * nout);
+  HIPCHK(hipMemcpyAsync(f.data(), d_f, f.size() * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+  if (count) HIPCHK(hipMemcpyAsync(count, d_c, nout * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  for (size_t i = 0; i < f.size(); i++) force[i] = f[i];
+  return MJH_OK;
+}
+#undef REPORT_ON
 
 // ---- height scans (mjh_heightscan / mjh_heightscan_device, heightscan.hip): the checks (dev_heightscan.h), the root-id table at the first
 // call with exclude_tree = 1, ray_scene() (with the body poses when the sensor is a site), then mjh_heightscan_kernel on the same stream.

@@ -940,6 +940,21 @@ DEV int pgs_many_body(const ManyCtx& c, const int lane) {
   return niter + nmain;
 }
 
+// Force of one contact block in its contact frame, on geom2's body (mj_contactForce for condim <= 4): normal, tangent 1, tangent 2, torque
+// about the normal.  hd0 = the block's first header word (kind | rows << 4), f = its row forces.  The pyramid's bases carry their friction
+// coefficient, so the signed row sums of a base ARE its force component (phi_from_forces); torsional base 3 = torque about the normal.
+// Shared by the external-force gather (sensors, cfrc_ext) and the contact report, so that the two decode every block kind alike.
+DEV void contact_frame_force(const int hd0, const float* f, const float mu1, const float mu3, float cf[4]) {
+  float ph[4] = {0, 0, 0, 0};
+  const int kind = hd0 & 15, nr = (hd0 >> 4) & 15;
+  for (int r = 0; r < nr; r++) {
+    const float fr = f[r];
+    ph[0] += fr;
+    if (kind != BK_SINGLE) { const int kk = 1 + (r >> 1); ph[kk] += (r & 1) ? -fr : fr; }
+  }
+  cf[0] = ph[0]; cf[1] = mu1 * ph[1]; cf[2] = mu1 * ph[2]; cf[3] = mu3 * ph[3];
+}
+
 // EXTRA: the model has a pair for the generic convex narrow phase (cylinder-x, capsule-box, ellipsoid-x, mesh geoms) or
 // asks for noslip sweeps; a separate instantiation so that models without either (S24, box piles, the robots'
 // primitive geometry) keep their code size and register allocation
@@ -1011,6 +1026,9 @@ __global__ __launch_bounds__(64, MJH_STEP_WAVES_T) void mjh_step_kernel(const DC
 #define MJH_COLLIDE_LANES 1
 #endif
   constexpr bool COLLIDE_LANES = MJH_COLLIDE_LANES != 0 && WPRE != 0;
+  // contact report (C->R, mjh_set_contact_report): an engine that reports is never a free-body (DIAGM) or window-chain one, so only the
+  // articulated EXTRA instances carry the stage; every other instance compiles exactly as before
+  constexpr bool REPORT = EXTRA && !DIAGM && WPRE == 0;
 #define LA(n) const XArr<MJH_LAZY_LDS, &Lay::n> s_##n(lds, L);
   MJH_LDS_SMALL(LA)
 #undef LA
@@ -1051,6 +1069,13 @@ __global__ __launch_bounds__(64, MJH_STEP_WAVES_T) void mjh_step_kernel(const DC
     for (int i = lane; i < nq; i += 64) S.qpos[qrow + i] = S.initial_qpos[qrow + i];
     for (int i = lane; i < nv; i += 64) { S.qvel[vrow+i] = 0; S.qacc_ws[vrow+i] = 0; S.qvel_ref[vrow+i] = 0; S.qfrc_applied[vrow+i] = 0; S.ddq[vrow+i] = 0; S.dq[vrow+i] = 0; }
     if (lane == 0) { S.time[env] = 0; S.stats[4*env] = 0; S.stats[4*env+1] = 0; S.stats[4*env+2] = 0; S.stats[4*env+3] = 0; }
+    if constexpr (REPORT) if (C->R.on) {   // the env's contact report: as before the first solve
+      const DReport& R = C->R;
+      float* const rec = R.rec + (size_t)env * (size_t)R.maxcon * CREP_STRIDE;
+      for (int i = lane; i < R.maxcon * CREP_STRIDE; i += 64) rec[i] = 0;
+      for (int i = lane; i < 6 * nbody; i += 64) R.cfrc[(size_t)env * (size_t)(6 * nbody) + i] = 0;
+      if (lane == 0) R.ncon[env] = 0;
+    }
     return;
   }
   for (int i = lane; i < nq; i += 64) s_qpos[i] = S.qpos[qrow + i];
@@ -2993,7 +3018,13 @@ step_again:      // (a backward goto instead of a `for`: the instances without t
         const size_t e = (size_t)xrow * M.nvp;
         for (int d = lane; d < nv; d += 64) { if (S.x_smooth) S.x_smooth[e + d] = s_asmooth[d]; if (S.x_constraint) S.x_constraint[e + d] = s_tmpv2[d]; }
       }
-      if (EXTRA && M.nsensor > 0 && S.sensordata && !post) {
+      if constexpr (EXTRA) {      // (discarded, not only dead, in the other instances: they compile exactly as before)
+      bool report = false;
+      if constexpr (REPORT) report = C->R.on != 0;
+      const bool sensors = M.nsensor > 0 && S.sensordata;
+      if ((sensors || report) && !post) {
+        // Three parts: (a) the gather of the external forces [sensors or contact report], (c) the contact report, (b) the RNE pass and the
+        // sensor read-out [sensors].
         // ---- mj_sensorAcc -> mj_rnePostConstraint (force / torque sensors; consumer: mj_ros.cpp:1933-1966).  External spatial
         //      force per body about its tree root's COM (xfrc_applied, contact forces, connect / weld forces), then the RNE
         //      forward pass with the SOLVED qacc, cfrc_int = cinert cacc + cvel x* (cinert cvel) - cfrc_ext summed over each
@@ -3013,24 +3044,18 @@ step_again:      // (a backward goto instead of a `for`: the instances without t
             if (xf) { const float f[3] = {xf[6*b], xf[6*b+1], xf[6*b+2]}, t[3] = {xf[6*b+3], xf[6*b+4], xf[6*b+5]}; add(s_xipos + 3*b, f, t, 1.0f); }
             for (int k = 0; k < nblk; k++) {
               const int* hd = s_blki_i + k * BLKI_STRIDE;
-              const int id = hd[1] & 0xffffff, rtype = (hd[1] >> 24) & 15, kind = hd[0] & 15;
+              const int id = hd[1] & 0xffffff, rtype = (hd[1] >> 24) & 15;
               const float* bf = s_blkf + k * BLKF_STRIDE;
               if (rtype == RT_CONTACT) {
                 const float* c = s_con + id * CON_STRIDE;
                 const int g1 = CON_G1(c), g2 = CON_G2(c);
                 const int b1 = geom_bodyid[g1], b2 = geom_bodyid[g2];
                 if (b1 != b && b2 != b) continue;
-                // contact-frame force on geom2's body: bases carry their friction coefficient, so the signed row sums of a
-                // base ARE its force component (phi_from_forces); torsional base 3 = torque about the normal
-                float ph[4] = {0, 0, 0, 0};
-                const int nr = (hd[0] >> 4) & 15;
-                for (int r = 0; r < nr; r++) {
-                  const float f = bf[BF_F + r];
-                  ph[0] += f;
-                  if (kind != BK_SINGLE) { const int kk = 1 + (r >> 1); ph[kk] += (r & 1) ? -f : f; }
-                }
+                // contact-frame force on geom2's body (contact_frame_force: the decoding the contact report shares)
                 const float mu1 = fmaxf(geom_friction[3*g1], geom_friction[3*g2]), mu3 = fmaxf(geom_friction[3*g1+1], geom_friction[3*g2+1]);
-                const float cf[3] = {ph[0], mu1 * ph[1], mu1 * ph[2]}, tors = mu3 * ph[3];
+                float cf[4];
+                contact_frame_force(hd[0], bf + BF_F, mu1, mu3, cf);
+                const float tors = cf[3];
                 float Fw[3], Tw[3];
 #pragma unroll
                 for (int q = 0; q < 3; q++) { Fw[q] = c[4+q] * cf[0] + c[7+q] * cf[1] + c[10+q] * cf[2]; Tw[q] = c[4+q] * tors; }
@@ -3067,6 +3092,42 @@ step_again:      // (a backward goto instead of a `for`: the instances without t
           for (int q = 0; q < 6; q++) s_fext[6*b+q] = F[q];
         }
         WSYNC();
+        if constexpr (REPORT) if (report) {
+          // ---- contact report (dev_types.h: DReport): the contacts of the collision stage with the forces of this solve, and cfrc_ext.
+          //      Lanes = blocks decode their force into the per-base scratch vector phi (dead since qfrc_constraint was formed; four floats per
+          //      block, and a model has at least as many block slots as contacts), lanes = contacts then write whole records: a contact that
+          //      got no rows (row capacity) keeps the zeros.
+          const DReport& R = C->R;
+          float* const rec = R.rec + (size_t)env * (size_t)R.maxcon * CREP_STRIDE;
+          for (int c = lane; c < ncon; c += 64) *(float4*)(s_phi + 4 * c) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+          WSYNC();
+          for (int k = lane; k < nblk; k += 64) {
+            const int* hd = s_blki_i + k * BLKI_STRIDE;
+            if (((hd[1] >> 24) & 15) != RT_CONTACT) continue;
+            const int id = hd[1] & 0xffffff;
+            if (id >= ncon) continue;
+            const float* c = s_con + id * CON_STRIDE;
+            const int g1 = CON_G1(c), g2 = CON_G2(c);
+            const float mu1 = fmaxf(geom_friction[3*g1], geom_friction[3*g2]), mu3 = fmaxf(geom_friction[3*g1+1], geom_friction[3*g2+1]);
+            float cf[4];
+            contact_frame_force(hd[0], s_blkf + k * BLKF_STRIDE + BF_F, mu1, mu3, cf);
+            *(float4*)(s_phi + 4 * id) = make_float4(cf[0], cf[1], cf[2], cf[3]);
+          }
+          WSYNC();
+          for (int c = lane; c < ncon; c += 64) {
+            const float4* r = (const float4*)(s_con + c * CON_STRIDE);
+            const float4 r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3], f = *(const float4*)(s_phi + 4 * c);
+            const int gw = __float_as_int(r3.y);     // [CON_GEOMS]
+            float4* o = (float4*)(rec + (size_t)c * CREP_STRIDE);
+            o[0] = r0; o[1] = r1; o[2] = r2;
+            o[3] = make_float4(r3.x, f.x, f.y, f.z);
+            o[4] = make_float4(f.w, __int_as_float(gw & 0xfff), __int_as_float((gw >> 12) & 0xfff), __int_as_float(gw >> 24));
+          }
+          if (lane == 0) R.ncon[env] = ncon;
+          for (int i = lane; i < 6 * nbody; i += 64) R.cfrc[(size_t)env * (size_t)(6 * nbody) + i] = s_fext[i];
+          WSYNC();
+        }
+        if (sensors) {
         // forward pass (as vel_levels with flg_acc), then cfrc_int and its subtree sums
         if (lane == 0) { for (int k = 0; k < 6; k++) { s_cvel[k] = 0; s_cacc[k] = (k >= 3) ? -grav[k-3] : 0.0f; s_cfrc[k] = 0; } }
         WSYNC();
@@ -3134,7 +3195,9 @@ step_again:      // (a backward goto instead of a `for`: the instances without t
           for (int k = 0; k < 3; k++) out[k] = sp[3+k] * src[0] + sp[6+k] * src[1] + sp[9+k] * src[2];     // R_site^T v
         }
         WSYNC();
+        }   // sensors
       }
+      }   // EXTRA
       if (ph & PH_STEP2) {
         // ---- mj_checkAcc
         bool badv = false;

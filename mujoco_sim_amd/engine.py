@@ -104,16 +104,33 @@ def scene(name, *args):
     return Model(fn(*args), lib)
 
 
+def set_contact_report(on):
+    """mjh_set_contact_report: engines created afterwards (process-wide); Engine(..., contact_report=True) sets it for one engine"""
+    capi.load().mjh_set_contact_report(1 if on else 0)
+
+
 EP = dict(geom_size=0, geom_rbound=1, body_mass=2, body_inertia=3, body_invweight0=4, dof_invweight0=5)
 
 
 class Engine:
-    def __init__(self, model, nenv, device=0, stream=None):
+    def __init__(self, model, nenv, device=0, stream=None, contact_report=False):
+        """contact_report: the engine leaves the contacts with their solver forces and cfrc_ext on the device after every solve
+        (mjh_set_contact_report around mjh_create; the process-wide switch is put back afterwards).  False leaves the switch as it is:
+        set_contact_report() or MJH_CONTACT_REPORT then decide, and `contact_report` tells what the engine does"""
         self.lib = model.lib
         self.model = model
         self.nenv = nenv
         h = C.c_void_p()
-        _chk(self.lib, self.lib.mjh_create(model.ptr, nenv, device, C.c_void_p(stream or 0), C.byref(h)), "mjh_create")
+        if contact_report:
+            probe_was = self.lib.mjh_contact_report(None)      # (no engine: the process-wide switch)
+            self.lib.mjh_set_contact_report(1)
+            try:
+                rc = self.lib.mjh_create(model.ptr, nenv, device, C.c_void_p(stream or 0), C.byref(h))
+            finally:
+                self.lib.mjh_set_contact_report(probe_was)
+            _chk(self.lib, rc, "mjh_create")
+        else:
+            _chk(self.lib, self.lib.mjh_create(model.ptr, nenv, device, C.c_void_p(stream or 0), C.byref(h)), "mjh_create")
         self.h = h
         self.nq, self.nv, self.nbody, self.ngeom = model.nq, model.nv, model.nbody, model.ngeom
 
@@ -248,6 +265,62 @@ class Engine:
         dist = np.zeros(mc); pos = np.zeros((mc, 3)); fr = np.zeros((mc, 9)); g = np.zeros((mc, 2), dtype=np.int32)
         n = _chk(self.lib, self.lib.mjh_get_contacts(self.h, env, capi.dptr(dist), capi.dptr(pos), capi.dptr(fr), capi.iptr(g)), "mjh_get_contacts")
         return dict(dist=dist[:n], pos=pos[:n], frame=fr[:n], geom=g[:n])
+
+    # ---- contact report (Engine(..., contact_report=True)): contacts with their solver forces, cfrc_ext, per-body contact force
+    @property
+    def contact_report(self):
+        """True when this engine leaves the contact report after every solve (mjh_contact_report)"""
+        return bool(self.lib.mjh_contact_report(self.h))
+
+    def contact_forces(self, env0=0, n=None):
+        """the report of the last solve: dict of ncon [n] and, per env, lists trimmed to its ncon: dist [k], pos [k, 3], frame [k, 9], force
+        [k, 6] (mj_contactForce's layout, contact frame, on geom2's body; entries 4 and 5 are zero), geom [k, 2], dim [k]"""
+        n = self.nenv - env0 if n is None else n
+        mc = self.model.maxcon
+        ncon = np.zeros(n, dtype=np.int32); dist = np.zeros((n, mc)); pos = np.zeros((n, mc, 3)); fr = np.zeros((n, mc, 9))
+        force = np.zeros((n, mc, 6)); geom = np.zeros((n, mc, 2), dtype=np.int32); dim = np.zeros((n, mc), dtype=np.int32)
+        _chk(self.lib, self.lib.mjh_get_contact_forces(self.h, env0, n, capi.iptr(ncon), capi.dptr(dist), capi.dptr(pos), capi.dptr(fr),
+                                                       capi.dptr(force), capi.iptr(geom), capi.iptr(dim)), "mjh_get_contact_forces")
+        trim = lambda a: [a[i, :ncon[i]].copy() for i in range(n)]
+        return dict(ncon=ncon, dist=trim(dist), pos=trim(pos), frame=trim(fr), force=trim(force), geom=trim(geom), dim=trim(dim))
+
+    def cfrc_ext(self, env0=0, n=None):
+        """d->cfrc_ext of the last solve [n, nbody, 6]: torque(3) force(3), world axes, about the subtree COM of the body's tree root"""
+        n = self.nenv - env0 if n is None else n
+        out = np.zeros((n, self.nbody, 6))
+        _chk(self.lib, self.lib.mjh_get_cfrc_ext(self.h, env0, n, capi.dptr(out)), "mjh_get_cfrc_ext")
+        return out
+
+    @staticmethod
+    def _selection(bodies, against):
+        b = np.ascontiguousarray(np.atleast_1d(bodies), dtype=np.int32)
+        a = None if against is None else np.ascontiguousarray(np.broadcast_to(np.atleast_1d(against), b.shape), dtype=np.int32)
+        return b, a
+
+    def body_contact_force(self, bodies, against=None, env0=0, n=None):
+        """net contact force ON each of `bodies` in world axes [n, nsel, 3] and the number of contacts in each sum [n, nsel];
+        against: per body the other body a contact must touch to count (-1 / None: any)"""
+        n = self.nenv - env0 if n is None else n
+        b, a = self._selection(bodies, against)
+        force = np.zeros((n, len(b), 3)); count = np.zeros((n, len(b)), dtype=np.int32)
+        _chk(self.lib, self.lib.mjh_body_contact_force(self.h, env0, n, len(b), capi.iptr(b), capi.iptr(a), capi.dptr(force), capi.iptr(count)),
+             "mjh_body_contact_force")
+        return force, count
+
+    def body_contact_force_device(self, d_force, d_count, bodies, against=None, env0=0, n=None):
+        """mjh_body_contact_force_device: device addresses (data_ptr()) of fp32 force [n, nsel, 3] and int32 count [n, nsel] (d_count may be
+        None); enqueued on the engine's stream, valid after synchronize()"""
+        n = self.nenv - env0 if n is None else n
+        b, a = self._selection(bodies, against)
+        _chk(self.lib, self.lib.mjh_body_contact_force_device(self.h, env0, n, len(b), capi.iptr(b), capi.iptr(a), C.c_void_p(d_force), C.c_void_p(d_count)),
+             "mjh_body_contact_force_device")
+
+    def contact_report_device(self):
+        """device addresses of the engine's report buffers: dict of ncon (int32 [nenv]), records (fp32 [nenv, maxcon, 20]), cfrc_ext
+        (fp32 [nenv, nbody, 6]) and maxcon; they belong to the engine and hold the last solve's report once its stream has reached it"""
+        p = [C.c_void_p(), C.c_void_p(), C.c_void_p()]; mc = C.c_int(0)
+        _chk(self.lib, self.lib.mjh_contact_report_device(self.h, C.byref(p[0]), C.byref(p[1]), C.byref(p[2]), C.byref(mc)), "mjh_contact_report_device")
+        return dict(ncon=p[0].value, records=p[1].value, cfrc_ext=p[2].value, maxcon=mc.value)
 
     def mulM(self, vec, env0=0):
         v = np.ascontiguousarray(vec, dtype=np.float64).reshape(-1, self.nv); r = np.zeros_like(v)
