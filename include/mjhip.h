@@ -889,6 +889,37 @@ int mjh_get_cfrc_ext(mjh_engine*, int env0, int n, double* cfrc_ext /* [n * 6 * 
  * MJH_ERR_ARG and launch nothing; a contact capacity beyond 3276 (the kernel's LDS stage) MJH_ERR_CAPACITY. */
 int mjh_body_contact_force_device(mjh_engine*, int env0, int n, int nsel, const int* body, const int* against, void* d_force, void* d_count);
 int mjh_body_contact_force(mjh_engine*, int env0, int n, int nsel, const int* body, const int* against, double* force, int* count);
+/* ------------------------------------------------- frame states: pose, twist and Jacobian of bodies and sites
+ * What the robot is doing in Cartesian terms, for every env, without a host round trip.  A frame is (objtype, id); its world pose is
+ *   body: xpos[b], xquat[b];   site: xpos[b] + R_b site_pos, xquat[b] * site_quat with b = site_bodyid.
+ * Jacobian (world axes, at the frame's world origin p; mj_jacBody / mj_jacSite): one column per dof of the frame's body and of its
+ * ancestors, every other column zero —
+ *   slide: jacp = axis, jacr = 0;   hinge: jacr = axis, jacp = axis x (p - anchor);
+ *   free joint: three translational columns with the world unit axes, then three rotational columns with the BODY's axes through xpos[b];
+ *   ball: three rotational columns with the body's axes (after the ball's rotation) through the joint anchor;
+ * axis and anchor of a joint taken with the body frame as it stands after the body's joints before it (mj_kinematics' order).
+ * Twist: linvel = jacp qvel, angvel = jacr qvel (mj_objectVelocity with flg_local = 0, the linear part first).
+ * Per frame: flags & MJH_FRAME_LOCAL rotates the twist into the frame's own axes (velocimeter / gyro; the pose stays the world pose);
+ * refid >= 0 reports pose and twist relative to the frame (reftype, refid), in its axes (MuJoCo's frame sensors with reftype):
+ *   pos = Rr^T (p - pr), quat = qr^-1 q, linvel = Rr^T (v - vr - wr x (p - pr)), angvel = Rr^T (w - wr);   refid = -1: no ref.
+ * Output per env and frame, 13 numbers: pos[3], quat[4] (w first), linvel[3], angvel[3].  The Jacobian is optional: [n][nframe][6][nv],
+ * rows 0-2 jacp, rows 3-5 jacr, always in world axes at the frame's world origin, whatever ref / LOCAL say.
+ * Poses and velocities are those of the envs' present qpos / qvel (after mjh_step: the state at the new time).  A mocap body reports the
+ * pose set per env, zero twist and a zero Jacobian; bodies of inactive slots are reported as they are.
+ * One position-stage launch of the env range (as mjh_get_body_state issues it) and one launch of mjh_frame_state_kernel (csrc/frame.hip) on
+ * the engine's stream behind the steps queued so far; nothing of the envs' state, statistics or time is written.  The frame table is
+ * uploaded only when it differs from the last call's; the per-model tables are built at the first call.  The order of the additions is
+ * fixed per env and frame: a result does not depend on nenv, env0, n, the other frames of the call or on whether a Jacobian was asked
+ * for (bitwise).  Device form: d_state float [n][nframe][13], d_jac float [n][nframe][6][nv] or NULL, no synchronisation.  Host form:
+ * doubles, synchronises; jac may be NULL.
+ * An env range out of bounds, nframe <= 0, an objtype other than 0 / 1, an id outside [0, nbody) / [0, nsite), a bad ref, LOCAL together
+ * with a ref, a NULL frames / state pointer, or n * nframe * 6 * nv beyond 2^30 with a Jacobian return MJH_ERR_ARG and launch nothing; an
+ * nv beyond 2048 (the kernel's LDS stage of 8 words per dof) MJH_ERR_CAPACITY.  Not forwarded by mjh_group, not part of the pinned mirror. */
+enum { MJH_FRAME_BODY = 0, MJH_FRAME_SITE = 1 };
+enum { MJH_FRAME_LOCAL = 1 };
+typedef struct mjh_frame { int objtype, id, reftype, refid, flags; } mjh_frame;
+int mjh_frame_state_device(mjh_engine*, int env0, int n, int nframe, const mjh_frame* frames, void* d_state, void* d_jac);
+int mjh_frame_state(mjh_engine*, int env0, int n, int nframe, const mjh_frame* frames, double* state, double* jac);
 int mjh_set_cohorts(mjh_engine*, int n);
 int mjh_get_cohorts(const mjh_engine*);
 /* mjh_step(e, n) of an articulated model in the LDS-resident layout runs up to `n` steps per launch and cohort with the environment's

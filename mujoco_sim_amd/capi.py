@@ -176,6 +176,9 @@ class HeightScanOptions(C.Structure):
                 ("offset", C.c_double * 2), ("above", C.c_double), ("bodyexclude", C.c_int), ("exclude_tree", C.c_int),
                 ("flg_static", C.c_int), ("cull", C.c_int), ("cutoff", C.c_double)]
 
+class Frame(C.Structure):
+    _fields_ = [("objtype", C.c_int), ("id", C.c_int), ("reftype", C.c_int), ("refid", C.c_int), ("flags", C.c_int)]
+
 class LightOptions(C.Structure):
     _fields_ = [("shadows", C.c_int), ("cull", C.c_int), ("bias", C.c_float)]
 
@@ -333,6 +336,8 @@ SYMBOLS = [
     ("mjh_get_cfrc_ext", C.c_int, [_vp, C.c_int, C.c_int, c_double_p]),
     ("mjh_body_contact_force_device", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, c_int_p, c_int_p, _vp, _vp]),
     ("mjh_body_contact_force", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, c_int_p, c_int_p, c_double_p, c_int_p]),
+    ("mjh_frame_state_device", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
+    ("mjh_frame_state", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, c_double_p, c_double_p]),
     ("mjh_set_pgs_row_order", None, [C.c_int]),
     ("mjh_set_cohorts", C.c_int, [_vp, C.c_int]),
     ("mjh_get_cohorts", C.c_int, [_vp]),

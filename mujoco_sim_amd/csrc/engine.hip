@@ -20,6 +20,7 @@
 #include "dev_scan.h"
 #include "dev_heightscan.h"
 #include "dev_contact.h"
+#include "dev_frame.h"
 #include "dev_render.h"
 #include "dev_light.h"
 #include "dev_texture.h"
@@ -152,6 +153,12 @@ struct mjh_engine {
   // height scans (mjh_heightscan / mjh_heightscan_device, heightscan.hip): the model's body_rootid on the device, uploaded at the first call
   // with exclude_tree = 1 (an engine that never asks has no such buffer)
   int* hscan_root = nullptr;
+  // frame states (mjh_frame_state / mjh_frame_state_device, frame.hip): the per-model tables, built and uploaded at the first call (freed with the
+  // engine's other allocations); the frame table of the last call on the device — the pinned host buffer the upload is issued from, the event
+  // that marks the upload's end — and the frames it holds (a call with the same ones uploads nothing); staging of the host form
+  bool frame_ready = false; FrameModel frame_model{};
+  FrameRec* frame_tab = nullptr; FrameRec* frame_host = nullptr; int frame_cap = 0; hipEvent_t frame_up = nullptr; std::vector<int> frame_have;
+  float* frame_io = nullptr; size_t frame_io_floats = 0;
 };
 
 static int pad32(int n) { return ((n + 31) / 32) * 32; }
@@ -852,6 +859,10 @@ extern "C" void mjh_destroy(mjh_engine* e) {
   if (e->csel_host) (void)hipHostFree(e->csel_host);
   if (e->csel_up) (void)hipEventDestroy(e->csel_up);
   if (e->csel_io) (void)hipFree(e->csel_io);
+  if (e->frame_tab) (void)hipFree(e->frame_tab);
+  if (e->frame_host) (void)hipHostFree(e->frame_host);
+  if (e->frame_up) (void)hipEventDestroy(e->frame_up);
+  if (e->frame_io) (void)hipFree(e->frame_io);
   if (e->h_dense) (void)hipHostFree(e->h_dense);
   if (e->h_wn) (void)hipHostFree(e->h_wn);
   if (e->h_io) (void)hipHostFree(e->h_io);
@@ -2408,6 +2419,153 @@ extern "C" int mjh_body_contact_force(mjh_engine* e, int env0, int n, int nsel, 
   return MJH_OK;
 }
 #undef REPORT_ON
+
+// ---- frame states (mjh_frame_state / mjh_frame_state_device, frame.hip): the checks, the per-model tables at the first call, the frame table
+// when it is not the last call's, the position-stage launch with the body poses (as fk_export issues it), then mjh_frame_state_kernel on the
+// same stream.  Nothing of the envs' state, statistics or time is written.
+// argument checks shared by both entry points: nothing is launched when one fails
+static int frame_check(const mjh_engine* e, int env0, int n, int nframe, const mjh_frame* frames, const void* state, bool jac) {
+  const mjh_model* m = e->model;
+  if (env0 < 0 || n <= 0 || env0 + n > e->nenv) { mjh_set_error("mjh_frame_state: env range out of bounds"); return MJH_ERR_ARG; }
+  if (nframe <= 0 || !frames || !state) { mjh_set_error("mjh_frame_state: no frames or null pointer"); return MJH_ERR_ARG; }
+  if ((long long)n * nframe * FR_STATE > (1ll << 30)) { mjh_set_error("mjh_frame_state: n * nframe too large"); return MJH_ERR_ARG; }
+  if (jac && (long long)n * nframe * 6 * (long long)m->nv > (1ll << 30)) { mjh_set_error("mjh_frame_state: n * nframe * 6 * nv beyond 2^30"); return MJH_ERR_ARG; }
+  for (int f = 0; f < nframe; f++) {
+    const mjh_frame& F = frames[f];
+    if (F.objtype != MJH_FRAME_BODY && F.objtype != MJH_FRAME_SITE) { mjh_set_error("mjh_frame_state: objtype is neither MJH_FRAME_BODY nor MJH_FRAME_SITE"); return MJH_ERR_ARG; }
+    if (F.id < 0 || F.id >= (F.objtype == MJH_FRAME_SITE ? m->nsite : m->nbody)) { mjh_set_error("mjh_frame_state: frame id out of range"); return MJH_ERR_ARG; }
+    if (F.flags & ~MJH_FRAME_LOCAL) { mjh_set_error("mjh_frame_state: unknown flag"); return MJH_ERR_ARG; }
+    if (F.refid < -1) { mjh_set_error("mjh_frame_state: bad ref"); return MJH_ERR_ARG; }
+    if (F.refid >= 0) {
+      if (F.reftype != MJH_FRAME_BODY && F.reftype != MJH_FRAME_SITE) { mjh_set_error("mjh_frame_state: reftype is neither MJH_FRAME_BODY nor MJH_FRAME_SITE"); return MJH_ERR_ARG; }
+      if (F.refid >= (F.reftype == MJH_FRAME_SITE ? m->nsite : m->nbody)) { mjh_set_error("mjh_frame_state: ref id out of range"); return MJH_ERR_ARG; }
+      if (F.flags & MJH_FRAME_LOCAL) { mjh_set_error("mjh_frame_state: MJH_FRAME_LOCAL together with a ref"); return MJH_ERR_ARG; }
+    }
+  }
+  if (frame_lds_bytes(m->nv) > FR_LDS_MAX) { mjh_set_error("mjh_frame_state: nv beyond the kernel's LDS stage"); return MJH_ERR_CAPACITY; }
+  return MJH_OK;
+}
+// the per-model tables of dev_frame.h, from the host model: one int buffer and one float buffer
+static int frame_tables(mjh_engine* e) {
+  if (e->frame_ready) return MJH_OK;
+  const mjh_model* m = e->model;
+  const int nv = m->nv, nb = m->nbody, nj = m->njnt, ns = m->nsite, nw = std::max(1, (nv + 31) / 32);
+  const size_t o_dof = 0, o_body = o_dof + 4 * (size_t)nv, o_jnt = o_body + 4 * (size_t)nb, o_chain = o_jnt + 2 * (size_t)nj, o_site = o_chain + (size_t)nb * nw;
+  std::vector<int> I(o_site + (size_t)ns + 4, 0);
+  for (int d = 0; d < nv; d++) {
+    const int j = m->dof_jntid[d];
+    I[o_dof + 4*d] = m->jnt_type[j]; I[o_dof + 4*d + 1] = d - m->jnt_dofadr[j]; I[o_dof + 4*d + 2] = m->dof_bodyid[d]; I[o_dof + 4*d + 3] = j;
+  }
+  for (int b = 0; b < nb; b++) {
+    I[o_body + 4*b] = m->body_parentid[b]; I[o_body + 4*b + 1] = m->body_jntadr[b]; I[o_body + 4*b + 2] = m->body_jntnum[b];
+    I[o_body + 4*b + 3] = (m->nmocap > 0 && m->body_mocapid) ? m->body_mocapid[b] : -1;
+    // the dofs that move the body: its own and its ancestors'
+    for (int a = b; a > 0; a = m->body_parentid[a])
+      for (int d = m->body_dofadr[a]; d < m->body_dofadr[a] + m->body_dofnum[a]; d++)
+        if (d >= 0 && d < nv) I[o_chain + (size_t)b * nw + (d >> 5)] |= (int)(1u << (d & 31));
+  }
+  for (int j = 0; j < nj; j++) { I[o_jnt + 2*j] = m->jnt_type[j]; I[o_jnt + 2*j + 1] = m->jnt_qposadr[j]; }
+  for (int s = 0; s < ns; s++) I[o_site + s] = m->site_bodyid[s];
+  const size_t f_bpos = 0, f_bquat = f_bpos + 3 * (size_t)nb, f_jpos = f_bquat + 4 * (size_t)nb, f_jaxis = f_jpos + 3 * (size_t)nj, f_q0 = f_jaxis + 3 * (size_t)nj,
+               f_spos = f_q0 + (size_t)m->nq, f_squat = f_spos + 3 * (size_t)ns;
+  std::vector<float> F(f_squat + 4 * (size_t)ns + 4, 0.0f);
+  for (int i = 0; i < 3 * nb; i++) F[f_bpos + i] = (float)m->body_pos[i];
+  for (int i = 0; i < 4 * nb; i++) F[f_bquat + i] = (float)m->body_quat[i];
+  for (int i = 0; i < 3 * nj; i++) { F[f_jpos + i] = (float)m->jnt_pos[i]; F[f_jaxis + i] = (float)m->jnt_axis[i]; }
+  for (int i = 0; i < m->nq; i++) F[f_q0 + i] = (float)m->qpos0[i];
+  for (int i = 0; i < 3 * ns; i++) F[f_spos + i] = (float)m->site_pos[i];
+  for (int i = 0; i < 4 * ns; i++) F[f_squat + i] = (float)m->site_quat[i];
+  int* dI = nullptr; float* dF = nullptr;
+  int rc = dev_alloc(e, &dI, I.size(), false);
+  if (!rc) rc = dev_alloc(e, &dF, F.size(), false);
+  if (rc) return rc;
+  HIPCHK(hipMemcpy(dI, I.data(), I.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dF, F.data(), F.size() * sizeof(float), hipMemcpyHostToDevice));
+  FrameModel& M = e->frame_model;
+  M.dof = (const int4*)(dI + o_dof); M.body = (const int4*)(dI + o_body); M.jnt = (const int2*)(dI + o_jnt);
+  M.chain = (const unsigned*)(dI + o_chain); M.site_body = dI + o_site;
+  M.body_pos = dF + f_bpos; M.body_quat = dF + f_bquat; M.jnt_pos = dF + f_jpos; M.jnt_axis = dF + f_jaxis; M.qpos0 = dF + f_q0;
+  M.site_pos = dF + f_spos; M.site_quat = dF + f_squat;
+  M.nv = nv; M.nbody = nb; M.njnt = nj; M.nsite = ns; M.nw = nw;
+  e->frame_ready = true;
+  return MJH_OK;
+}
+// the (checked) frames in e->frame_tab: uploaded in stream order from the engine's pinned buffer unless they are there already
+static int frame_table(mjh_engine* e, int nframe, const mjh_frame* frames) {
+  std::vector<int> want((size_t)5 * nframe);
+  for (int f = 0; f < nframe; f++) {
+    const bool ref = frames[f].refid >= 0;
+    want[5*f] = frames[f].objtype; want[5*f+1] = frames[f].id; want[5*f+2] = ref ? frames[f].reftype : 0; want[5*f+3] = ref ? frames[f].refid : -1; want[5*f+4] = frames[f].flags;
+  }
+  if (e->frame_tab && want == e->frame_have) return MJH_OK;
+  e->frame_have.clear();
+  if (!e->frame_up) HIPCHK(hipEventCreateWithFlags(&e->frame_up, hipEventDisableTiming));
+  else HIPCHK(hipEventSynchronize(e->frame_up));      // (the last upload has read the host buffer)
+  if (nframe > e->frame_cap) {
+    if (e->frame_host) { HIPCHK(hipHostFree(e->frame_host)); e->frame_host = nullptr; }
+    if (e->frame_tab) { HIPCHK(hipStreamSynchronize(e->stream)); HIPCHK(hipFree(e->frame_tab)); e->frame_tab = nullptr; }
+    e->frame_cap = 0;
+    HIPCHK(hipHostMalloc((void**)&e->frame_host, (size_t)nframe * sizeof(FrameRec), hipHostMallocDefault));
+    HIPCHK(hipMalloc((void**)&e->frame_tab, (size_t)nframe * sizeof(FrameRec)));
+    e->frame_cap = nframe;
+  }
+  const mjh_model* m = e->model;
+  for (int f = 0; f < nframe; f++) {
+    const mjh_frame& F = frames[f];
+    FrameRec R{};
+    R.site = F.objtype == MJH_FRAME_SITE ? F.id : -1; R.body = R.site >= 0 ? m->site_bodyid[R.site] : F.id;
+    R.ref = F.refid >= 0 ? 1 : 0; R.rbody = 0; R.rsite = -1;
+    if (R.ref) { R.rsite = F.reftype == MJH_FRAME_SITE ? F.refid : -1; R.rbody = R.rsite >= 0 ? m->site_bodyid[R.rsite] : F.refid; }
+    R.local = (F.flags & MJH_FRAME_LOCAL) ? 1 : 0;
+    e->frame_host[f] = R;
+  }
+  HIPCHK(hipMemcpyAsync(e->frame_tab, e->frame_host, (size_t)nframe * sizeof(FrameRec), hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipEventRecord(e->frame_up, e->stream));
+  e->frame_have = want;
+  return MJH_OK;
+}
+extern "C" int mjh_frame_state_device(mjh_engine* e, int env0, int n, int nframe, const mjh_frame* frames, void* d_state, void* d_jac) {
+  ENG(e);
+  int rc = frame_check(e, env0, n, nframe, frames, d_state, d_jac != nullptr);
+  if (rc) return rc;
+  rc = frame_tables(e);
+  if (!rc) rc = frame_table(e, nframe, frames);
+  if (rc) return rc;
+  const int nb = e->M.nbody;
+  const size_t fx = (size_t)n * 3 * nb, fq = (size_t)n * 4 * nb;
+  rc = ensure_scratch(e, fx + fq);
+  if (rc) return rc;
+  {
+    StateGuard guard(&e->S);
+    e->S.x_xpos = e->scratch; e->S.x_xquat = e->scratch + fx;
+    rc = launch(e, env0, n, 1, PH_FKONLY, XF_BODY);
+  }
+  if (rc) return rc;
+  FrameArgs A{};
+  A.M = e->frame_model;
+  A.xpos = e->scratch; A.xquat = e->scratch + fx; A.qpos = e->S.qpos; A.qvel = e->S.qvel; A.frames = e->frame_tab;
+  A.state = (float*)d_state; A.jac = (float*)d_jac;
+  A.env0 = env0; A.n = n; A.nframe = nframe; A.nqp = e->M.nqp; A.nvp = e->M.nvp;
+  HIPCHK(mjh_launch_frame_state(e->stream, A));
+  return MJH_OK;
+}
+extern "C" int mjh_frame_state(mjh_engine* e, int env0, int n, int nframe, const mjh_frame* frames, double* state, double* jac) {
+  ENG(e);
+  int rc = frame_check(e, env0, n, nframe, frames, state, jac != nullptr);
+  if (rc) return rc;
+  const size_t ns = (size_t)n * nframe * FR_STATE, nj = jac ? (size_t)n * nframe * 6 * (size_t)e->M.nv : 0;
+  rc = io_reserve(e, &e->frame_io, &e->frame_io_floats, ns + nj);
+  if (rc) return rc;
+  float* const d_s = e->frame_io; float* const d_j = nj ? e->frame_io + ns : nullptr;
+  rc = mjh_frame_state_device(e, env0, n, nframe, frames, d_s, jac ? (void*)(nj ? d_j : d_s) : nullptr);
+  if (rc) return rc;
+  std::vector<float> h(ns + nj);
+  HIPCHK(hipMemcpyAsync(h.data(), d_s, h.size() * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  for (size_t i = 0; i < ns; i++) state[i] = h[i];
+  for (size_t i = 0; i < nj; i++) jac[i] = h[ns + i];
+  return MJH_OK;
+}
 
 // ---- height scans (mjh_heightscan / mjh_heightscan_device, heightscan.hip): the checks (dev_heightscan.h), the root-id table at the first
 // call with exclude_tree = 1, ray_scene() (with the body poses when the sensor is a site), then mjh_heightscan_kernel on the same stream.

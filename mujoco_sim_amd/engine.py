@@ -322,6 +322,68 @@ class Engine:
         _chk(self.lib, self.lib.mjh_contact_report_device(self.h, C.byref(p[0]), C.byref(p[1]), C.byref(p[2]), C.byref(mc)), "mjh_contact_report_device")
         return dict(ncon=p[0].value, records=p[1].value, cfrc_ext=p[2].value, maxcon=mc.value)
 
+    # ---- frame states: pose, twist and Jacobian of bodies and sites (mjh_frame_state)
+    _FRAME_TYPES = {"body": (0, 0), "site": (1, 3)}      # name -> (MJH_FRAME_*, objtype of mjh_name2id)
+
+    def _frame_id(self, item, what):
+        kind, ref = item
+        if kind not in self._FRAME_TYPES:
+            raise MjhError(f"{what}: frame type {kind!r} is neither 'body' nor 'site'")
+        code, objtype = self._FRAME_TYPES[kind]
+        if isinstance(ref, str):
+            i = self.model.name2id(objtype, ref)
+            if i < 0:
+                raise MjhError(f"{what}: no {kind} named {ref!r}")
+            return code, i
+        return code, int(ref)
+
+    def _frame_table(self, frames):
+        """frames: items ("body" | "site", name_or_id[, ref=("body" | "site", name_or_id)][, local=True]) — the options as a dict behind
+        the two entries, or a dict(type=, id=, ref=, local=) — or a capi.Frame array already resolved; names are resolved once per distinct
+        list (the table is kept)"""
+        if isinstance(frames, C.Array) and frames._type_ is capi.Frame:
+            return frames
+        key = repr(frames)
+        cache = self.__dict__.setdefault("_frame_cache", {})
+        if key in cache:
+            return cache[key]
+        tab = (capi.Frame * len(frames))()
+        for k, it in enumerate(frames):
+            if isinstance(it, dict):
+                head, opt = (it["type"], it["id"]), {a: b for a, b in it.items() if a not in ("type", "id")}
+            else:
+                head, opt = tuple(it[:2]), dict(it[2]) if len(it) > 2 else {}
+            unknown = set(opt) - {"ref", "local"}
+            if unknown:
+                raise MjhError(f"frame_state: unknown frame option {sorted(unknown)}")
+            tab[k].objtype, tab[k].id = self._frame_id(head, "frame_state")
+            tab[k].reftype, tab[k].refid = (0, -1) if opt.get("ref") is None else self._frame_id(opt["ref"], "frame_state ref")
+            tab[k].flags = 1 if opt.get("local") else 0
+        cache[key] = tab
+        return tab
+
+    def frame_state(self, frames, env0=0, n=None, jacobian=False):
+        """world (or ref-relative) pose and twist of bodies and sites at the envs' present qpos / qvel: dict of float64 arrays pos [n, nframe, 3],
+        quat [n, nframe, 4] (w first), linvel, angvel [n, nframe, 3] and, with jacobian=True, jacp, jacr [n, nframe, 3, nv] (world axes, at the
+        frame's world origin).  frames: see _frame_table, e.g. [("body", "base"), ("site", "tip", dict(ref=("body", "base"))), ("site", 2, dict(local=True))]"""
+        n = self.nenv - env0 if n is None else n
+        tab = self._frame_table(frames)
+        nf = len(tab)
+        st = np.zeros((n, nf, 13)); jac = np.zeros((n, nf, 6, self.nv)) if jacobian else None
+        _chk(self.lib, self.lib.mjh_frame_state(self.h, env0, n, nf, C.cast(tab, C.c_void_p), capi.dptr(st), capi.dptr(jac)), "mjh_frame_state")
+        out = dict(pos=st[..., 0:3].copy(), quat=st[..., 3:7].copy(), linvel=st[..., 7:10].copy(), angvel=st[..., 10:13].copy())
+        if jacobian:
+            out["jacp"] = jac[:, :, 0:3].copy(); out["jacr"] = jac[:, :, 3:6].copy()
+        return out
+
+    def frame_state_device(self, d_state, d_jac, frames, env0=0, n=None):
+        """mjh_frame_state_device: device addresses (data_ptr()) of fp32 state [n, nframe, 13] and Jacobian [n, nframe, 6, nv] (d_jac may be
+        None); enqueued on the engine's stream, valid after synchronize()"""
+        n = self.nenv - env0 if n is None else n
+        tab = self._frame_table(frames)
+        _chk(self.lib, self.lib.mjh_frame_state_device(self.h, env0, n, len(tab), C.cast(tab, C.c_void_p), C.c_void_p(d_state), C.c_void_p(d_jac)),
+             "mjh_frame_state_device")
+
     def mulM(self, vec, env0=0):
         v = np.ascontiguousarray(vec, dtype=np.float64).reshape(-1, self.nv); r = np.zeros_like(v)
         _chk(self.lib, self.lib.mjh_mulM(self.h, env0, v.shape[0], capi.dptr(v), capi.dptr(r)), "mjh_mulM")
