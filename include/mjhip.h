@@ -442,6 +442,18 @@ int mjh_synchronize(mjh_engine*);
  * host-mapped staging ring and does not wait for the device (stream-ordered in front of the
  * range's next step launch), larger ones copy and wait. */
 int mjh_set_cmd(mjh_engine*, int env0, int n, const double* ddq, const double* dq);
+/* Device forms of the control side of the loop (mjh_set_cmd_device, mjh_set_pd_target_device, mjh_set_xfrc_applied_device,
+ * mjh_get_joint_state_device, mjh_reset_device): a controller or policy on the same GPU exchanges actions, joint state and episode resets
+ * with the engine without a host copy, a conversion or a synchronisation.
+ * Contract of all five: device buffers are dense fp32 rows [n][width]; row i belongs to env env0 + i.  A call is enqueued and returns
+ * without waiting for the device; it reads or writes its buffers in stream order on the engine's stream (the stream given to mjh_create).
+ * The caller orders the producer (setters, reset) or the consumer (getter) of a buffer on that stream and keeps the buffer alive until the
+ * stream has passed the call.  Bits are copied: for fp32-representable values a setter leaves exactly what its host counterpart leaves
+ * (which rounds double to float).  The pointers are not inspected: a host address handed in here faults on the device.
+ * Not forwarded by mjh_group; not meant to be captured into a caller's graph.
+ * mjh_set_cmd_device: [n][nv] each, either may be NULL (both: no-op).  Like mjh_set_cmd it keeps a hand-over pending between mjh_step1 and
+ * mjh_step2, and a range inside one cohort touches that cohort's stream only. */
+int mjh_set_cmd_device(mjh_engine*, int env0, int n, const float* d_ddq, const float* d_dq);
 /* In-engine joint-space PD effort controller for ALL environments.  The reference closes this loop on the host for its one
  * environment: read() -> controller_manager->update() -> write() (mj_main.cpp:86-106) with ros_control effort controllers
  * (PID p 200 d 50: model/ontology/box/box.yaml:5-13) whose output MjSim::controller treats as a desired acceleration
@@ -451,6 +463,8 @@ int mjh_set_cmd(mjh_engine*, int env0, int n, const double* ddq, const double* d
  * mjh_set_pd_target takes [n*nv] values indexed by dof. */
 int mjh_set_pd_controller(mjh_engine*, double kp, double kd);
 int mjh_set_pd_target(mjh_engine*, int env0, int n, const double* target);
+/* device form (contract: see mjh_set_cmd_device): d_target [n][nv]; MJH_ERR_STATE until the controller has been enabled */
+int mjh_set_pd_target_device(mjh_engine*, int env0, int n, const float* d_target);
 /* which dofs are "controlled" (MjSim::controlled_joints, mj_sim.cpp:1058-1063): mask[nv] */
 int mjh_set_controlled_dofs(mjh_engine*, const int* mask);
 /* MjSim::set_odom_vels (mj_sim.cpp:1079-1153): dof ids of the 6 odom joints of one
@@ -464,6 +478,9 @@ int mjh_set_odom_vel(mjh_engine*, int env0, int n, const double* twist);
  * small kernel into host-mapped memory (one synchronisation), larger ranges take strided copies */
 int mjh_get_joint_state(mjh_engine*, int env0, int n, double* qpos, double* qvel,
                         double* qfrc_inverse);
+/* device form (contract: see mjh_set_cmd_device): d_qpos [n][nq], d_qvel [n][nv], d_qfrc_inverse [n][nv], any may be NULL; the rows are
+ * written behind the steps queued on the range's stream, nothing is waited for (qfrc_inverse is what the caller's mjh_inverse left) */
+int mjh_get_joint_state_device(mjh_engine*, int env0, int n, float* d_qpos, float* d_qvel, float* d_qfrc_inverse);
 /* d->xpos / d->xquat readers (mj_ros.cpp:2100-2147) */
 int mjh_get_body_state(mjh_engine*, int env0, int n, double* xpos, double* xquat);
 /* d->geom_xpos / geom_xmat readers (mj_ros.cpp:1968-2094) */
@@ -492,6 +509,9 @@ int mjh_get_contacts(mjh_engine*, int env, double* dist, double* pos, double* fr
 /* d->xfrc_applied (mj_sim.cpp:499 carries it across a model change): Cartesian force (3) and torque (3) per body, world
  * frame, applied at the body's centre of mass; [n * 6*nbody].  Enters qfrc_smooth of every step until changed. */
 int mjh_set_xfrc_applied(mjh_engine*, int env0, int n, const double* xfrc);
+/* device form (contract: see mjh_set_cmd_device): d_xfrc [n][6*nbody].  The first call of either form on an engine allocates the array
+ * and waits for the device once; none after it does. */
+int mjh_set_xfrc_applied_device(mjh_engine*, int env0, int n, const float* d_xfrc);
 int mjh_get_xfrc_applied(mjh_engine*, int env0, int n, double* xfrc);
 /* d->sensordata (mj_ros.cpp:1933-1966 reads sensordata[sensor_adr[i] .. +3] of every force / torque sensor): [n * nsensordata],
  * computed at the end of mj_step2's forward part (mj_sensorAcc), i.e. the values of the LAST step */
@@ -512,6 +532,14 @@ int mjh_set_env_param(mjh_engine*, int which, int env0, int n, const double* val
 int mjh_transplant_state(mjh_engine* from, mjh_engine* to, int qpos_mode);
 int mjh_set_initial_qpos(mjh_engine*, int env0, int n, const double* qpos);
 int mjh_reset(mjh_engine*, const int* env_ids, int n);
+/* (env_ids NULL: every env, and the launch scheduling starts over; a list of n >= 2 ids, in any order, duplicates allowed, is one upload
+ * and one launch, and leaves the scheduling state alone like a single id)
+ * Masked reset from device buffers (contract: see mjh_set_cmd_device): every env of [env0, env0 + n) with d_mask[i] != 0 (d_mask NULL:
+ * all of them) gets what mjh_reset does to one env: qpos = its initial qpos, qvel / qacc_warmstart / the pending command / time / solver
+ * statistics = 0, its contact report cleared.  With d_qpos [n][nq] or d_qvel [n][nv] a selected env takes its row from there instead, as
+ * given (not normalised, like mjh_set_state); rows of envs that are not selected are not read, and those envs are not written.  Drops a
+ * hand-over pending between mjh_step1 and mjh_step2. */
+int mjh_reset_device(mjh_engine*, int env0, int n, const unsigned char* d_mask, const float* d_qpos, const float* d_qvel);
 
 /* spawn / destroy as per-env slot toggling (reference: spawn_objects / destroy_objects services,
  * mj_ros.cpp:859-1507, which re-compile the whole model): an inactive slot does not collide and is frozen.

@@ -17,7 +17,7 @@ DENSE_HEADERS = ["dense_pgs.h"] + KERNEL_HEADERS
 WINDOW_HEADERS = ["window_kernel.h", "window_tiles.h", "step_kernel.h", "patch_pgs.h", "window_pgs.h", "dev_math.h", "dev_collide.h", "dev_convex.h", "dev_types.h"]
 # source -> headers it includes (besides itself)
 SOURCES = {
-    "engine.hip": KERNEL_HEADERS + ["dev_ray.h", "ray_bvh.h", "dev_depth.h", "dev_scan.h", "dev_heightscan.h", "dev_contact.h", "dev_frame.h", "dev_render.h", "dev_light.h", "dev_texture.h", "ray_tables.h", API],
+    "engine.hip": KERNEL_HEADERS + ["dev_ray.h", "ray_bvh.h", "dev_depth.h", "dev_scan.h", "dev_heightscan.h", "dev_contact.h", "dev_frame.h", "dev_control.h", "dev_render.h", "dev_light.h", "dev_texture.h", "ray_tables.h", API],
     "window.hip": WINDOW_HEADERS + [API],
     "dense.hip": DENSE_HEADERS + [API],
     "hfield.hip": KERNEL_HEADERS + [API],
@@ -27,6 +27,7 @@ SOURCES = {
     "heightscan.hip": ["dev_heightscan.h", "dev_scan.h", "dev_depth.h", "dev_ray.h", "ray_bvh.h", API],
     "contact.hip": ["dev_contact.h", API],
     "frame.hip": ["dev_frame.h", "dev_math.h", API],
+    "control.hip": ["dev_control.h", "dev_types.h", API],
     "render.hip": ["dev_render.h", "dev_depth.h", "dev_ray.h", "ray_bvh.h", API],
     "light.hip": ["dev_light.h", "dev_render.h", "dev_depth.h", "dev_ray.h", "ray_bvh.h", API],
     "texture.hip": ["dev_texture.h", "dev_render.h", "dev_depth.h", "dev_ray.h", "ray_bvh.h", API],

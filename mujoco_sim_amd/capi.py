@@ -338,6 +338,11 @@ SYMBOLS = [
     ("mjh_body_contact_force", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, c_int_p, c_int_p, c_double_p, c_int_p]),
     ("mjh_frame_state_device", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
     ("mjh_frame_state", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, c_double_p, c_double_p]),
+    ("mjh_set_cmd_device", C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
+    ("mjh_set_pd_target_device", C.c_int, [_vp, C.c_int, C.c_int, _vp]),
+    ("mjh_set_xfrc_applied_device", C.c_int, [_vp, C.c_int, C.c_int, _vp]),
+    ("mjh_get_joint_state_device", C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+    ("mjh_reset_device", C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     ("mjh_set_pgs_row_order", None, [C.c_int]),
     ("mjh_set_cohorts", C.c_int, [_vp, C.c_int]),
     ("mjh_get_cohorts", C.c_int, [_vp]),

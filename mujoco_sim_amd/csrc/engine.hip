@@ -21,6 +21,7 @@
 #include "dev_heightscan.h"
 #include "dev_contact.h"
 #include "dev_frame.h"
+#include "dev_control.h"
 #include "dev_render.h"
 #include "dev_light.h"
 #include "dev_texture.h"
@@ -159,6 +160,9 @@ struct mjh_engine {
   bool frame_ready = false; FrameModel frame_model{};
   FrameRec* frame_tab = nullptr; FrameRec* frame_host = nullptr; int frame_cap = 0; hipEvent_t frame_up = nullptr; std::vector<int> frame_have;
   float* frame_io = nullptr; size_t frame_io_floats = 0;
+  // mjh_reset with an id list (control.hip): the ids of a call go through a ring of pinned slots, each fenced by an event like the slots of
+  // mjh_set_cmd, into one device buffer (rewritten in stream order); rid_cap ints per slot, grown to the longest list seen
+  int* rid_host = nullptr; int* rid_dev = nullptr; size_t rid_cap = 0; hipEvent_t rid_ev[MJH_IO_SLOTS] = {}; bool rid_used[MJH_IO_SLOTS] = {}; unsigned rid_next = 0;
 };
 
 static int pad32(int n) { return ((n + 31) / 32) * 32; }
@@ -863,6 +867,9 @@ extern "C" void mjh_destroy(mjh_engine* e) {
   if (e->frame_host) (void)hipHostFree(e->frame_host);
   if (e->frame_up) (void)hipEventDestroy(e->frame_up);
   if (e->frame_io) (void)hipFree(e->frame_io);
+  if (e->rid_host) (void)hipHostFree(e->rid_host);
+  if (e->rid_dev) (void)hipFree(e->rid_dev);
+  for (int k = 0; k < MJH_IO_SLOTS; k++) if (e->rid_ev[k]) (void)hipEventDestroy(e->rid_ev[k]);
   if (e->h_dense) (void)hipHostFree(e->h_dense);
   if (e->h_wn) (void)hipHostFree(e->h_wn);
   if (e->h_io) (void)hipHostFree(e->h_io);
@@ -1232,6 +1239,57 @@ extern "C" int mjh_set_cmd(mjh_engine* e, int env0, int n, const double* ddq, co
   return put_rows(e, e->S.dq, e->M.nvp, e->M.nv, env0, n, dq, st);
 }
 
+// ---- device forms (control.hip): dense fp32 rows [n][width] of the caller's device buffers <-> the engine's rows, enqueued on the range's
+// stream; no host copy, no conversion, no synchronisation.  The caller orders the buffers' producer / consumer on the engine's stream.
+struct RowPart { float* eng; int stride, width; const void* buf; };
+static int move_rows(hipStream_t st, int env0, int n, const RowPart* parts, int nparts, bool scatter) {
+  ControlRowsArgs A{};
+  A.env0 = env0; A.n = n;
+  int k = 0;
+  for (int i = 0; i < nparts; i++) if (parts[i].buf && parts[i].width > 0) {
+    A.eng[k] = parts[i].eng; A.stride[k] = parts[i].stride; A.width[k] = parts[i].width; A.buf[k] = (float*)parts[i].buf; k++;
+  }
+  if (k == 0 || n <= 0) return MJH_OK;
+  HIPCHK(scatter ? mjh_launch_scatter_rows(st, A) : mjh_launch_gather_rows(st, A));
+  return MJH_OK;
+}
+// A move of the rows [env0, env0 + n) that leaves the cohorts forked (commands and the joint state: what a loop issues between two steps).
+// Not forked: one launch on the engine's stream.  Forked: every cohort moves its part of the range on its own stream, right behind its last
+// step, as mjh_export_state_device does; the caller's buffers are ordered on the engine's stream, so each of those streams is bracketed
+// against it — it waits for what the engine's stream holds so far (the buffer's producer), and the engine's stream waits for the move (the
+// buffer's consumer, or its release).  Events only, no host wait, and a cohort the range does not touch is left alone.  The rows written are
+// those of the joined form.
+static int move_rows_forked(mjh_engine* e, int env0, int n, const RowPart* parts, int nparts, bool scatter) {
+  const int G = e->ncohort;
+  if (!e->forked || G <= 1 || e->nenv < 64 * G) {
+    int rc = join_cohorts(e);
+    return rc ? rc : move_rows(e->stream, env0, n, parts, nparts, scatter);
+  }
+  HIPCHK(hipEventRecord(e->ev_fork, e->stream));
+  for (int g = 0; g < G; g++) {
+    const int g0 = (int)((long long)e->nenv * g / G), g1 = (int)((long long)e->nenv * (g + 1) / G);
+    const int lo = std::max(env0, g0), hi = std::min(env0 + n, g1);
+    if (lo >= hi) continue;
+    RowPart sub[CTL_MAXPART];
+    for (int i = 0; i < nparts; i++) {
+      sub[i] = parts[i];
+      if (sub[i].buf) sub[i].buf = (const float*)sub[i].buf + (size_t)(lo - env0) * (size_t)sub[i].width;
+    }
+    HIPCHK(hipStreamWaitEvent(e->cstream[g], e->ev_fork, 0));
+    int rc = move_rows(e->cstream[g], lo, hi - lo, sub, nparts, scatter);
+    if (rc) return rc;
+    HIPCHK(hipEventRecord(e->ev_join[g], e->cstream[g]));
+    HIPCHK(hipStreamWaitEvent(e->stream, e->ev_join[g], 0));
+  }
+  return MJH_OK;
+}
+extern "C" int mjh_set_cmd_device(mjh_engine* e, int env0, int n, const float* d_ddq, const float* d_dq) {
+  ENG_NOJOIN(e); KEEP_HANDOVER(e); RANGE(e, env0, n);
+  if ((!d_ddq && !d_dq) || n == 0) return MJH_OK;
+  const RowPart parts[2] = {{e->S.ddq, e->M.nvp, e->M.nv, d_ddq}, {e->S.dq, e->M.nvp, e->M.nv, d_dq}};
+  return move_rows_forked(e, env0, n, parts, 2, true);
+}
+
 // ---- in-engine PD effort controller.  The reference runs ros_control effort controllers on the host between read() and
 // write() (mj_main.cpp:86-106; gains e.g. PID p 200 d 50, model/ontology/box/box.yaml:5-13) for its ONE environment; with
 // thousands of environments that hand-off is a PCIe round trip per step, so the same law can run on the device: in front of
@@ -1279,6 +1337,13 @@ extern "C" int mjh_set_pd_target(mjh_engine* e, int env0, int n, const double* t
   if (!target) return MJH_ERR_ARG;
   if (!e->pd_target) { mjh_set_error("mjh_set_pd_target: enable the controller first (mjh_set_pd_controller)"); return MJH_ERR_STATE; }
   return put_rows(e, e->pd_target, e->M.nv, e->M.nv, env0, n, target);
+}
+extern "C" int mjh_set_pd_target_device(mjh_engine* e, int env0, int n, const float* d_target) {
+  ENG(e); RANGE(e, env0, n);
+  if (!d_target) { mjh_set_error("mjh_set_pd_target_device: null target"); return MJH_ERR_ARG; }
+  if (!e->pd_target) { mjh_set_error("mjh_set_pd_target_device: enable the controller first (mjh_set_pd_controller)"); return MJH_ERR_STATE; }
+  const RowPart part = {e->pd_target, e->M.nv, e->M.nv, d_target};
+  return move_rows(e->stream, env0, n, &part, 1, true);
 }
 
 static int patch_int_table(mjh_engine* e, int off, const int* vals, int n) {
@@ -1343,6 +1408,12 @@ extern "C" int mjh_get_joint_state(mjh_engine* e, int env0, int n, double* qpos,
   HIPCHK(hipStreamSynchronize(st));
   for (int k = 0; k < 3; k++) if (dst[k]) for (size_t i = 0; i < tmp[k].size(); i++) dst[k][i] = (double)tmp[k][i];
   return MJH_OK;
+}
+extern "C" int mjh_get_joint_state_device(mjh_engine* e, int env0, int n, float* d_qpos, float* d_qvel, float* d_qfrc_inverse) {
+  ENG_NOJOIN(e); KEEP_HANDOVER(e); RANGE(e, env0, n);
+  if (n == 0 || (!d_qpos && !d_qvel && !d_qfrc_inverse)) return MJH_OK;
+  const RowPart parts[3] = {{e->S.qpos, e->M.nqp, e->M.nq, d_qpos}, {e->S.qvel, e->M.nvp, e->M.nv, d_qvel}, {e->S.qfrc_inverse, e->M.nvp, e->M.nv, d_qfrc_inverse}};
+  return move_rows_forked(e, env0, n, parts, 3, false);
 }
 
 // position-stage recompute for a range of envs with export pointers set
@@ -1546,18 +1617,31 @@ extern "C" int mjh_set_env_param(mjh_engine* e, int which, int env0, int n, cons
 }
 
 // d->xfrc_applied (mj_sim.cpp:499): force + torque per body at its centre of mass, world frame
+// first use: the zeroed per-env array (from then on the engine takes the EXTRA instances of the step kernel); waits for the device once
+static int ensure_xfrc(mjh_engine* e) {
+  if (e->S.xfrc_applied) return MJH_OK;
+  const int w = 6 * e->M.nbody;
+  const int stride = ((w + 3) / 4) * 4;
+  int rc = dev_alloc(e, &e->S.xfrc_applied, (size_t)e->nenv * stride);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(e->stream));
+  e->S.xfrc_stride = stride;
+  return MJH_OK;
+}
 extern "C" int mjh_set_xfrc_applied(mjh_engine* e, int env0, int n, const double* xfrc) {
   ENG(e); RANGE(e, env0, n);
   if (!xfrc) return MJH_ERR_ARG;
-  const int w = 6 * e->M.nbody;
-  if (!e->S.xfrc_applied) {
-    const int stride = ((w + 3) / 4) * 4;
-    int rc = dev_alloc(e, &e->S.xfrc_applied, (size_t)e->nenv * stride);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(e->stream));
-    e->S.xfrc_stride = stride;
-  }
-  return put_rows(e, e->S.xfrc_applied, e->S.xfrc_stride, w, env0, n, xfrc);
+  int rc = ensure_xfrc(e);
+  if (rc) return rc;
+  return put_rows(e, e->S.xfrc_applied, e->S.xfrc_stride, 6 * e->M.nbody, env0, n, xfrc);
+}
+extern "C" int mjh_set_xfrc_applied_device(mjh_engine* e, int env0, int n, const float* d_xfrc) {
+  ENG(e); RANGE(e, env0, n);
+  if (!d_xfrc) { mjh_set_error("mjh_set_xfrc_applied_device: null xfrc"); return MJH_ERR_ARG; }
+  int rc = ensure_xfrc(e);
+  if (rc) return rc;
+  const RowPart part = {e->S.xfrc_applied, e->S.xfrc_stride, 6 * e->M.nbody, d_xfrc};
+  return move_rows(e->stream, env0, n, &part, 1, true);
 }
 extern "C" int mjh_get_xfrc_applied(mjh_engine* e, int env0, int n, double* xfrc) {
   ENG(e); RANGE(e, env0, n);
@@ -1607,17 +1691,62 @@ static int reset_dense_choice(mjh_engine* e) {
   e->order_age = 0; e->order_G = -1;
   return MJH_OK;
 }
+// ids (already checked against nenv) -> next pinned slot -> the device buffer -> one launch of the reset kernel, all on the caller's stream.
+// A slot is rewritten MJH_IO_SLOTS calls later, after its event (the end of its upload); the device buffer is rewritten in stream order.
+static int reset_id_list(mjh_engine* e, const int* ids, int n) {
+  if ((size_t)n > e->rid_cap) {
+    size_t cap = 1024;
+    while (cap < (size_t)n) cap *= 2;
+    if (e->rid_host) {      // (uploads and launches in flight still read the old buffers)
+      HIPCHK(hipStreamSynchronize(e->stream));
+      HIPCHK(hipHostFree(e->rid_host)); e->rid_host = nullptr;
+      HIPCHK(hipFree(e->rid_dev)); e->rid_dev = nullptr;
+      e->rid_cap = 0;
+      for (int k = 0; k < MJH_IO_SLOTS; k++) e->rid_used[k] = false;
+    }
+    HIPCHK(hipHostMalloc((void**)&e->rid_host, (size_t)MJH_IO_SLOTS * cap * sizeof(int), hipHostMallocDefault));
+    HIPCHK(hipMalloc((void**)&e->rid_dev, cap * sizeof(int)));
+    for (int k = 0; k < MJH_IO_SLOTS; k++) if (!e->rid_ev[k]) HIPCHK(hipEventCreateWithFlags(&e->rid_ev[k], hipEventDisableTiming));
+    e->rid_cap = cap;
+  }
+  const unsigned slot = e->rid_next++ % MJH_IO_SLOTS;
+  if (e->rid_used[slot]) HIPCHK(hipEventSynchronize(e->rid_ev[slot]));
+  int* const h = e->rid_host + (size_t)slot * e->rid_cap;
+  std::memcpy(h, ids, (size_t)n * sizeof(int));
+  HIPCHK(hipMemcpyAsync(e->rid_dev, h, (size_t)n * sizeof(int), hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipEventRecord(e->rid_ev[slot], e->stream)); e->rid_used[slot] = true;
+  ControlResetArgs A{};
+  A.C = e->dC; A.S = e->S; A.ids = e->rid_dev; A.env0 = 0; A.n = n;
+  HIPCHK(mjh_launch_reset_rows(e->stream, A));
+  return MJH_OK;
+}
 extern "C" int mjh_reset(mjh_engine* e, const int* env_ids, int n) {
   ENG(e);
   if (!env_ids) {
     if (e->h_wn) for (int g = 0; g < MJH_MAX_COHORTS; g++) e->h_wn[g] = 1 << 20;     // (row counts of the old state: keep the window kernel's LDS tier until the next look)
     int rc = reset_dense_choice(e); return rc ? rc : launch(e, 0, e->nenv, 1, PH_RESET, 0);
   }
+  if (n >= 2) {
+    // a list: checked as a whole, then ONE upload and ONE launch of the reset kernel (control.hip) instead of a launch of the step kernel per id
+    for (int i = 0; i < n; i++) if (env_ids[i] < 0 || env_ids[i] >= e->nenv) { mjh_set_error("mjh_reset: env id out of range"); return MJH_ERR_ARG; }
+    return reset_id_list(e, env_ids, n);
+  }
   for (int i = 0; i < n; i++) {
     if (env_ids[i] < 0 || env_ids[i] >= e->nenv) { mjh_set_error("mjh_reset: env id out of range"); return MJH_ERR_ARG; }
     int rc = launch(e, env_ids[i], 1, 1, PH_RESET, 0);
     if (rc) return rc;
   }
+  return MJH_OK;
+}
+// Masked reset of a range from device buffers: every env of [env0, env0 + n) with d_mask[i] != 0 (all of them without a mask) gets what
+// mjh_reset does to one env, its qpos / qvel row from d_qpos / d_qvel where given; the others are neither read nor written.  Like mjh_reset
+// with an id list it leaves launch order, dense choice and h_wn alone; it drops a pending hand-over (the state it was built from changes).
+extern "C" int mjh_reset_device(mjh_engine* e, int env0, int n, const unsigned char* d_mask, const float* d_qpos, const float* d_qvel) {
+  ENG(e); RANGE(e, env0, n);
+  if (n == 0) return MJH_OK;
+  ControlResetArgs A{};
+  A.C = e->dC; A.S = e->S; A.mask = d_mask; A.ids = nullptr; A.qpos = d_qpos; A.qvel = d_qvel; A.env0 = env0; A.n = n;
+  HIPCHK(mjh_launch_reset_rows(e->stream, A));
   return MJH_OK;
 }
 

@@ -112,6 +112,36 @@ def set_contact_report(on):
 EP = dict(geom_size=0, geom_rbound=1, body_mass=2, body_inertia=3, body_invweight0=4, dof_invweight0=5)
 
 
+def device_buffer(buf, name, count, device=0, dtypes=("float32",)):
+    """Address of a device buffer argument of the *_device calls.  None -> None and an integer address is taken as is.  An object with
+    data_ptr() (a torch tensor) must have one of `dtypes`, be contiguous, hold exactly `count` elements and live on CUDA/HIP device
+    `device`; each failure raises MjhError naming the argument.  This check is what keeps a host tensor's address from reaching a kernel."""
+    if buf is None:
+        return None
+    if isinstance(buf, (int, np.integer)):
+        return int(buf)
+    if not hasattr(buf, "data_ptr"):
+        raise MjhError(f"{name}: expected a device address or an object with data_ptr(), got {type(buf).__name__}")
+    dtype = str(buf.dtype).split(".")[-1]
+    if dtype not in dtypes:
+        raise MjhError(f"{name}: dtype {dtype}, expected {' or '.join(dtypes)}")
+    if not buf.is_contiguous():
+        raise MjhError(f"{name}: not contiguous")
+    if int(buf.numel()) != int(count):
+        raise MjhError(f"{name}: {int(buf.numel())} elements, expected {int(count)}")
+    dev = buf.device
+    if dev.type != "cuda" or (dev.index if dev.index is not None else 0) != device:
+        raise MjhError(f"{name}: on device {dev}, expected cuda:{device} (the engine's)")
+    return int(buf.data_ptr())
+
+
+def _buffer_rows(buf, width):
+    """rows of a buffer argument of width `width`, or None for an address / None"""
+    if buf is None or not hasattr(buf, "data_ptr"):
+        return None
+    return int(buf.shape[0]) if buf.dim() >= 2 else int(buf.numel()) // max(width, 1)
+
+
 class Engine:
     def __init__(self, model, nenv, device=0, stream=None, contact_report=False):
         """contact_report: the engine leaves the contacts with their solver forces and cfrc_ext on the device after every solve
@@ -120,6 +150,7 @@ class Engine:
         self.lib = model.lib
         self.model = model
         self.nenv = nenv
+        self.device = device
         h = C.c_void_p()
         if contact_report:
             probe_was = self.lib.mjh_contact_report(None)      # (no engine: the process-wide switch)
@@ -135,10 +166,10 @@ class Engine:
         self.nq, self.nv, self.nbody, self.ngeom = model.nq, model.nv, model.nbody, model.ngeom
 
     @classmethod
-    def from_handle(cls, model, handle, nenv):
+    def from_handle(cls, model, handle, nenv, device=0):
         """view of an engine owned by someone else (a device of an mjh_group): close() does not destroy it"""
         self = cls.__new__(cls)
-        self.lib = model.lib; self.model = model; self.nenv = nenv; self.h = C.c_void_p(handle); self._borrowed = True
+        self.lib = model.lib; self.model = model; self.nenv = nenv; self.h = C.c_void_p(handle); self._borrowed = True; self.device = device
         self.nq, self.nv, self.nbody, self.ngeom = model.nq, model.nv, model.nbody, model.ngeom
         return self
 
@@ -427,6 +458,49 @@ class Engine:
         else:
             ids = np.ascontiguousarray(env_ids, dtype=np.int32)
             _chk(self.lib, self.lib.mjh_reset(self.h, capi.iptr(ids), ids.shape[0]), "mjh_reset")
+
+    # ---- the loop on the device (mjh_*_device of the control side): actions, joint state and resets between device buffers and the engine.
+    # Every buffer is an integer device address (taken as is) or an object with data_ptr() such as a torch tensor (checked: device_buffer);
+    # dense fp32 rows [n, width], row i = env env0 + i.  The calls are enqueued on the engine's stream and wait for nothing: the caller orders
+    # the producer / consumer of a buffer on that stream and keeps the buffer alive until the stream has passed the call.
+    def _device_rows(self, what, env0, n, bufs):
+        """bufs: (argument name, buffer, row width, dtypes) each -> (n, addresses as c_void_p); n: the rows of the first tensor given, else
+        nenv - env0"""
+        if n is None:
+            n = next((r for r in (_buffer_rows(b, w) for _, b, w, _ in bufs) if r is not None), self.nenv - env0)
+        n = int(n)
+        return n, [C.c_void_p(device_buffer(b, f"{what}: {name}", n * w, self.device, dt)) for name, b, w, dt in bufs]
+
+    def set_cmd_device(self, ddq=None, dq=None, env0=0, n=None):
+        """mjh_set_cmd_device: fp32 ddq / dq [n, nv] on the device (either may be None)"""
+        f = ("float32",)
+        n, p = self._device_rows("set_cmd_device", env0, n, [("ddq", ddq, self.nv, f), ("dq", dq, self.nv, f)])
+        _chk(self.lib, self.lib.mjh_set_cmd_device(self.h, env0, n, p[0], p[1]), "mjh_set_cmd_device")
+
+    def set_pd_target_device(self, target, env0=0, n=None):
+        """mjh_set_pd_target_device: fp32 targets [n, nv] on the device"""
+        n, p = self._device_rows("set_pd_target_device", env0, n, [("target", target, self.nv, ("float32",))])
+        _chk(self.lib, self.lib.mjh_set_pd_target_device(self.h, env0, n, p[0]), "mjh_set_pd_target_device")
+
+    def set_xfrc_applied_device(self, xfrc, env0=0, n=None):
+        """mjh_set_xfrc_applied_device: fp32 force + torque per body [n, nbody, 6] on the device"""
+        n, p = self._device_rows("set_xfrc_applied_device", env0, n, [("xfrc", xfrc, 6 * self.nbody, ("float32",))])
+        _chk(self.lib, self.lib.mjh_set_xfrc_applied_device(self.h, env0, n, p[0]), "mjh_set_xfrc_applied_device")
+
+    def get_joint_state_device(self, qpos=None, qvel=None, qfrc_inverse=None, env0=0, n=None):
+        """mjh_get_joint_state_device: fills fp32 qpos [n, nq], qvel [n, nv], qfrc_inverse [n, nv] on the device (any may be None)"""
+        f = ("float32",)
+        n, p = self._device_rows("get_joint_state_device", env0, n,
+                                 [("qpos", qpos, self.nq, f), ("qvel", qvel, self.nv, f), ("qfrc_inverse", qfrc_inverse, self.nv, f)])
+        _chk(self.lib, self.lib.mjh_get_joint_state_device(self.h, env0, n, p[0], p[1], p[2]), "mjh_get_joint_state_device")
+
+    def reset_device(self, mask=None, qpos=None, qvel=None, env0=0, n=None):
+        """mjh_reset_device: resets the envs of [env0, env0 + n) whose mask byte (uint8 / bool [n]) is not zero (mask None: all of them); a
+        selected env takes its row of fp32 qpos [n, nq] / qvel [n, nv] where given, else its initial qpos / zero"""
+        f = ("float32",)
+        n, p = self._device_rows("reset_device", env0, n,
+                                 [("mask", mask, 1, ("uint8", "bool")), ("qpos", qpos, self.nq, f), ("qvel", qvel, self.nv, f)])
+        _chk(self.lib, self.lib.mjh_reset_device(self.h, env0, n, p[0], p[1], p[2]), "mjh_reset_device")
 
     def transplant_state_from(self, other, full_qpos=True):
         """add_old_state() (mj_sim.cpp:465-558): name-matched copy of the per-body state of `other` into this engine"""
@@ -790,7 +864,7 @@ class Group:
             a, b = C.c_int(0), C.c_int(0)
             _chk(self.lib, self.lib.mjh_group_env_range(h, k, C.byref(a), C.byref(b)), "mjh_group_env_range")
             self.ranges.append((a.value, b.value))
-            self.engines.append(Engine.from_handle(model, self.lib.mjh_group_engine(h, k), b.value))
+            self.engines.append(Engine.from_handle(model, self.lib.mjh_group_engine(h, k), b.value, int(dv[k])))
         self.stride = self.lib.mjh_group_state_stride(h)
 
     @property
