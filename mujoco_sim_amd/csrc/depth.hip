@@ -2,19 +2,16 @@
 // own: no instance of the step or ray kernels is touched.  The position-stage launch (PH_FKONLY, engine.hip: ray_scene) has exported
 // the envs' geom and body poses; this kernel only reads them, the per-env geom sizes and the slot masks, and writes the images.  The
 // rays exist in registers only: generated from the camera's intrinsics and its body's pose in the env.  To the shared code of
-// dev_ray.h it adds the pixel ray, the tile cone and its test, the compaction of the survivors and `range`.  gfx950 only.
+// dev_ray.h it adds the pixel ray, the tile cone and its test, and `range`.  gfx950 only.
 #include <hip/hip_runtime.h>
 
 #include "../../include/mjhip.h"
 #include "dev_depth.h"
 
-// One workgroup (one wavefront) per (env, tile of DEPTH_TILE x DEPTH_TILE pixels), one pixel per lane.  The env's geom records are
-// staged RAY_PASS geoms per pass (one per lane), but only the visible geoms whose bounding sphere touches the tile's cone reach LDS:
-// the survivors are compacted by ballot and a lane prefix count, in ascending geom id (so ties break as in ray.hip), and the walk never
-// meets a record of type -1.  cull = 0 skips the cone test only: generation and intersection are the same instructions, so the images
-// are the same bits.
-static __device__ __forceinline__ float uniform(float x) { return ray_float(ray_uniform(ray_bits(x))); }
-
+// One workgroup (one wavefront) per (env, tile of DEPTH_TILE x DEPTH_TILE pixels), one pixel per lane.  The
+// env's geom records are staged RAY_PASS geoms per pass by ray_stage (dev_ray.h): only the visible geoms whose bounding sphere touches
+// the tile's cone reach LDS, compacted in ascending geom id, and the walk never meets a record of type -1.  cull = 0 skips the cone test
+// only: generation and intersection are the same instructions, so the images are the same bits.
 // TRI: the instance for scenes with triangle tables (mesh surface 1; dev_ray.h: ray_walk); the other one is the kernel as it was.
 // amdgpu_num_sgpr(96) (no effect on the instance without, which takes 89): with the triangle walk of dev_ray.h (a node and a triangle record in scalar registers on top of the cone and the
 // scene's pointers) the kernel would take 106 scalar registers, one wave per SIMD fewer than the 8 its LDS allows.  Capped, six values
@@ -26,6 +23,9 @@ __global__ __launch_bounds__(RAY_TILE) __attribute__((amdgpu_num_sgpr(96))) void
   __shared__ float s_rec[RAY_PASS * RAY_REC];
   const RayScene& W = A.W;
   const int lane = (int)threadIdx.x;
+  // The tile map in this kernel's own text, not tile_row / tile_map of dev_depth.h (the same map; the other five kernels call them), and
+  // A.cull read in the predicate, not from a local: with either the prologue is scheduled otherwise, and such builds ran this kernel
+  // 0.4 - 1.0 % slower.  As written the unit's instruction sequence is the one it had before the shared pass (HISTORY.md, "One staging pass").
   const int tx = (A.width + DEPTH_TILE - 1) / DEPTH_TILE, ty = (A.height + DEPTH_TILE - 1) / DEPTH_TILE, ntile = tx * ty;
   const int row = (int)blockIdx.x / ntile, tile = (int)blockIdx.x - row * ntile;
   if (row >= W.n) return;
@@ -61,32 +61,14 @@ __global__ __launch_bounds__(RAY_TILE) __attribute__((amdgpu_num_sgpr(96))) void
 
   float best = -1.0f; int bestg = -1;
   for (int base = 0; base < W.ngeom; base += RAY_PASS) {
-    __syncthreads();
-    const int g = base + lane;
-    // stage geom g of this env: the verdict first (type, body, bounding sphere), then only a survivor's record is read and stored
-    int4 gi = make_int4(-1, 0, 0, 0);
-    float c[3] = {0.0f, 0.0f, 0.0f}, s[3] = {0.0f, 0.0f, 0.0f}, rb = 0.0f;
-    bool keep = false;
-    if (g < W.ngeom) {
-      gi = W.ginfo[g];
-      const float* gp = W.gpos + ((size_t)row * W.ngeom + g) * 3;
-#pragma unroll
-      for (int k = 0; k < 3; k++) c[k] = gp[k];
-#pragma unroll
-      for (int k = 0; k < 3; k++) s[k] = gsize[3*g + k];
-      keep = ray_verdict<TRI>(W, gi, s, slotmask, rb, &A.T) >= 0;
-      if (keep && A.cull && gi.x >= MJH_GEOM_SPHERE) {      // planes and height fields are never culled
+    const int cnt = ray_stage<TRI>(W, &A.T, s_rec, row, base, lane, slotmask, gsize, [=](bool keep, const int4 gi, const float* c, float rb) {
+      if (keep && A.cull && ray_cullable(gi)) {
         const float rel[3] = {c[0] - p[0], c[1] - p[1], c[2] - p[2]};
         keep = depth_cone_keep(axis, cosA, sinA, rel, rb);
       }
-    }
-    const unsigned long long kept = __ballot(keep);
-    if (keep) {      // the survivors in ascending geom id: record `number of survivors in the lanes below`
-      const int slot = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(kept >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)kept, 0u));
-      ray_store(s_rec + slot * RAY_REC, c, W.gmat + ((size_t)row * W.ngeom + g) * 9, s, rb, gi.x, gi.w, g);
-    }
-    __syncthreads();
-    ray_walk<false, TRI>(W, s_rec, __popcll(kept), p, v, vv, valid, best, bestg, &A.T);
+      return keep;
+    });
+    ray_walk<false, TRI>(W, s_rec, cnt, p, v, vv, valid, best, bestg, &A.T);
   }
   // dc.z = -1: the ray parameter is the depth along the optical axis; range: the distance from the camera origin
   if (A.range) best *= sqrtf(vv);
@@ -101,9 +83,5 @@ __global__ __launch_bounds__(RAY_TILE) __attribute__((amdgpu_num_sgpr(96))) void
 
 hipError_t mjh_launch_depth(hipStream_t st, const DepthArgs& A) {
   if (A.W.n <= 0 || A.width <= 0 || A.height <= 0) return hipErrorInvalidValue;
-  const long long tx = (A.width + DEPTH_TILE - 1) / DEPTH_TILE, ty = (A.height + DEPTH_TILE - 1) / DEPTH_TILE, blocks = tx * ty * (long long)A.W.n;
-  if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-  if (A.T.mesh) hipLaunchKernelGGL(mjh_depth_kernel<true>, dim3((unsigned)blocks), dim3(RAY_TILE), 0, st, A);
-  else hipLaunchKernelGGL(mjh_depth_kernel<false>, dim3((unsigned)blocks), dim3(RAY_TILE), 0, st, A);
-  return hipGetLastError();
+  return RAY_LAUNCH_TRI(mjh_depth_kernel, A.T, tile_blocks(A.width, A.height, DEPTH_TILE_LOG, A.W.n), st, A);
 }

@@ -6,7 +6,21 @@
 
 #include "dev_ray.h"
 
-#define DEPTH_TILE 8   // a wavefront renders a DEPTH_TILE x DEPTH_TILE pixel tile: column lane & 7, row lane >> 3
+#define DEPTH_TILE_LOG 3
+#define DEPTH_TILE (1 << DEPTH_TILE_LOG)   // a wavefront renders a DEPTH_TILE x DEPTH_TILE pixel tile: column lane & 7, row lane >> 3
+
+// The tile map of the image kernels (depth, shade, light, texture: tw_log = DEPTH_TILE_LOG; scan, heightscan: a launch argument,
+// dev_scan.h: scan_tile_shape): a width x height image is cut into tiles of TH x TW lanes, TW = 1 << tw_log, TH = RAY_TILE >> tw_log, a
+// lane's row in its tile is lane >> tw_log and its column lane & (TW - 1); one workgroup per (env row, tile), the tiles of an env row by
+// row.  tile_blocks: the workgroups of a launch over n envs.
+static __host__ __device__ __forceinline__ int tile_columns(int width, int tw_log) { return (width + (1 << tw_log) - 1) >> tw_log; }
+static __host__ __device__ __forceinline__ int tile_rows(int height, int tw_log) { return (height + (RAY_TILE >> tw_log) - 1) >> (6 - tw_log); }
+static inline long long tile_blocks(int width, int height, int tw_log, int n) {
+  return (long long)tile_columns(width, tw_log) * (long long)tile_rows(height, tw_log) * (long long)n;
+}
+// what workgroup `block` of env row `row` and its lane `lane` hold: the tile's first pixel (i0, j0) and its extent inside the image
+// (ni, nj), the lane's pixel (pi, pj) and whether it lies inside the image (live)
+struct TileMap { int i0, j0, ni, nj, pi, pj; bool live; };
 
 struct DepthArgs {
   RayScene W;
@@ -21,6 +35,23 @@ struct DepthArgs {
 hipError_t mjh_launch_depth(hipStream_t st, const DepthArgs& A);   // depth.hip
 
 #ifdef __HIPCC__
+// Integers only; with a literal tw_log they fold.  Two steps, because the kernel tests `row >= n` (a workgroup beyond the launch's env
+// rows returns at once) between them: with the test behind tile_map's division the kernel's first loads wait for it (HISTORY.md).
+static __device__ __forceinline__ int tile_row(int block, int width, int height, int tw_log) {
+  return block / (tile_columns(width, tw_log) * tile_rows(height, tw_log));
+}
+static __device__ __forceinline__ TileMap tile_map(int block, int row, int lane, int width, int height, int tw_log) {
+  const int TW = 1 << tw_log, TH = RAY_TILE >> tw_log;
+  const int tx = tile_columns(width, tw_log), ntile = tx * tile_rows(height, tw_log);
+  const int tile = block - row * ntile, trow = tile / tx, tcol = tile - trow * tx;
+  TileMap t;
+  t.i0 = trow * TH; t.j0 = tcol << tw_log;
+  t.ni = min(TH, height - t.i0); t.nj = min(TW, width - t.j0);
+  t.pi = t.i0 + (lane >> tw_log); t.pj = t.j0 + (lane & (TW - 1));
+  t.live = t.pi < height && t.pj < width;
+  return t;
+}
+
 // the ray through the centre of pixel (row i from the top, column j from the left) in the camera frame (looks along -z, +x right, +y up):
 // d = (a t (2 (j + 1/2) / W - 1), t (1 - 2 (i + 1/2) / H), -1) with a = W / H, so both factors are t / H = scale.  The integer
 // numerators are exact in fp32: each component carries one rounding besides that of `scale`.

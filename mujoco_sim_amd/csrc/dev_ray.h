@@ -1,7 +1,9 @@
-// dev_ray.h — what the ray kernel (ray.hip) and the depth kernel (depth.hip) share: the scene descriptor the host side (engine.hip)
-// fills, the fp32 ray-geom intersections in the geom's own frame, and the code that takes a ray through an env's geoms — the frame
-// composition, the verdict on a geom, the staged record and the walk over the records.  All of it is __host__ __device__:
-// tests/ray_host builds it for the CPU and checks the very code the kernels run.  gfx950 only.
+// dev_ray.h — what the ray kernel (ray.hip) and the kernels that trace per tile (depth.hip, scan.hip, heightscan.hip, light.hip) share:
+// the scene descriptor the host side (engine.hip) fills, the fp32 ray-geom intersections in the geom's own frame, and the code that
+// takes a ray through an env's geoms — the frame composition, the verdict on a geom, the staged record, the walk over the records,
+// the compacting staging pass (ray_stage) and the launch (ray_launch).  All but the last two is __host__ __device__: tests/ray_host
+// builds it for the CPU and checks the very code the kernels run (the staging pass is wave code: the host tests stage sequentially).
+// gfx950 only.
 //
 // Every intersection takes the ray origin p and direction v in the geom frame (v NOT normalised) and returns the smallest x >= 0 with
 // p + x v on the geom's surface, or -1.  Quadratics are solved about the point of closest approach (x = tc -+ sqrt(h2 / a) with
@@ -295,6 +297,7 @@ RDEV int ray_uniform(int x) {
 }
 RDEV int ray_bits(float x) { return __builtin_bit_cast(int, x); }
 RDEV float ray_float(int x) { return __builtin_bit_cast(float, x); }
+static __device__ __forceinline__ float uniform(float x) { return ray_float(ray_uniform(ray_bits(x))); }
 
 // A mesh's own triangles (ray_bvh.h: the records, the threaded BVH and the slack).  ray_tri is Moeller-Trumbore in fp32, two-sided:
 // with P = v x e2, det = e1.P, T = p - a, Q = T x e1 the hit is u = T.P / det, w = v.Q / det, x = e2.Q / det.
@@ -494,4 +497,54 @@ RDEV void ray_walk(const RayScene& W, const float* recs, int cnt, const float* p
     if (x >= 0.0f && (bestg < 0 || x < best)) { best = x; bestg = ray_bits(rec[18]); }
   }
 }
+
+// planes and height fields are never culled: the types a tile's bound (cone, cylinder, shadow segment) may drop
+RDEV bool ray_cullable(const int4 gi) { return gi.x >= MJH_GEOM_SPHERE; }
+
+// One staging pass of the kernels that trace per tile (depth, scan, heightscan, light): the RAY_PASS geoms of env row `row` from `base`
+// on, one per lane — the verdict first (type, body, bounding sphere), then the caller's own predicate, and only a survivor's record is
+// read and stored.  The survivors are compacted into s_rec by ballot and a lane prefix count, in ascending geom id (so ties break as in
+// ray.hip); their number is returned for ray_walk<false>.  Both barriers are inside: every lane of the wave must call it.  Device only;
+// position is loaded before size and nothing is interleaved (HISTORY.md).  No floating-point arithmetic of its own.
+// keep_geom(keep, gi, c, rb) -> keep: `keep` is the verdict, c the world position, rb the bounding radius.  A predicate only ever
+// clears it, every clause behind `keep &&`, so nothing is evaluated for a geom the verdict dropped.  Two things about its form are
+// measured, not taste (HISTORY.md, "One staging pass ..."): it takes and returns `keep` (called as `if (keep) keep = pred(...)` the
+// compiler keeps one more exec mask alive across the pass, and the kernels capped at 96 scalar registers spill up to six more values to
+// lanes: the height scan ran 2 % slower); and it is a lambda that captures BY VALUE ([=]) scalars and short arrays copied into locals
+// (by reference the kernel's wave-uniform values reach the walk's sums as loads through the closure, the compiler orders their
+// operands differently and fuses other products into the FMAs: other bits in the height scan's images).
+template <bool TRI, class Keep>
+static __device__ __forceinline__ int ray_stage(const RayScene& W, const RayTris* T, float* s_rec, int row, int base, int lane, unsigned slotmask, const float* gsize, Keep keep_geom) {
+  __syncthreads();
+  const int g = base + lane;
+  int4 gi = make_int4(-1, 0, 0, 0);
+  float c[3] = {0.0f, 0.0f, 0.0f}, s[3] = {0.0f, 0.0f, 0.0f}, rb = 0.0f;
+  bool keep = false;
+  if (g < W.ngeom) {
+    gi = W.ginfo[g];
+    const float* gp = W.gpos + ((size_t)row * W.ngeom + g) * 3;
+#pragma unroll
+    for (int k = 0; k < 3; k++) c[k] = gp[k];
+#pragma unroll
+    for (int k = 0; k < 3; k++) s[k] = gsize[3*g + k];
+    keep = keep_geom(ray_verdict<TRI>(W, gi, s, slotmask, rb, T) >= 0, gi, c, rb);
+  }
+  const unsigned long long kept = __ballot(keep);
+  if (keep) {      // record `number of survivors in the lanes below`
+    const int slot = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(kept >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)kept, 0u));
+    ray_store(s_rec + slot * RAY_REC, c, W.gmat + ((size_t)row * W.ngeom + g) * 9, s, rb, gi.x, gi.w, g);
+  }
+  __syncthreads();
+  return __popcll(kept);
+}
+
+// the launch of every kernel of these units: `blocks` workgroups of one wavefront each, refused when no grid holds that many.
+// RAY_LAUNCH_TRI takes the <true> instance of a kernel template where the scene has triangle tables (T.mesh), else <false>.
+template <class Args>
+static inline hipError_t ray_launch(void (*kernel)(const Args), long long blocks, hipStream_t st, const Args& A) {
+  if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(RAY_TILE), 0, st, A);
+  return hipGetLastError();
+}
+#define RAY_LAUNCH_TRI(kernel, T, blocks, st, A) ray_launch((T).mesh ? kernel<true> : kernel<false>, blocks, st, A)
 #endif

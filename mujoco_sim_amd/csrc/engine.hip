@@ -2230,6 +2230,30 @@ static int io_reserve(mjh_engine* e, float** buf, size_t* have, size_t need) {
 }
 // the device staging buffer of mjh_ray, mjh_depth and mjh_render
 static int ray_io_reserve(mjh_engine* e, size_t need) { return io_reserve(e, &e->ray_io, &e->ray_io_floats, need); }
+// a site's frame in its body for a launch descriptor (RayArgs, ScanArgs, HScanArgs); site < 0: the world frame
+template <class Args>
+static void site_frame(const mjh_model* m, int site, Args* A) {
+  A->site_body = -1;
+  if (site < 0) return;
+  A->site_body = m->site_bodyid[site];
+  for (int k = 0; k < 3; k++) A->site_pos[k] = (float)m->site_pos[3 * site + k];
+  for (int k = 0; k < 4; k++) A->site_quat[k] = (float)m->site_quat[4 * site + k];
+}
+// the host form of a scan (mjh_scan, mjh_heightscan): range, geom id and points of `nout` beams carved out of the staging buffer,
+// device(d_range, d_geomid, d_points) with null where the caller takes none, then read back in stream order
+template <class Device>
+static int scan_readback(mjh_engine* e, size_t nout, float* range, int* geomid, float* points, Device device) {
+  int rc = ray_io_reserve(e, 5 * nout);
+  if (rc) return rc;
+  float* const d_range = e->ray_io; int* const d_gid = (int*)(e->ray_io + nout); float* const d_pts = e->ray_io + 2 * nout;
+  rc = device(d_range, geomid ? d_gid : nullptr, points ? d_pts : nullptr);
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(range, d_range, nout * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+  if (geomid) HIPCHK(hipMemcpyAsync(geomid, d_gid, nout * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  if (points) HIPCHK(hipMemcpyAsync(points, d_pts, 3 * nout * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return MJH_OK;
+}
 extern "C" int mjh_ray_device(mjh_engine* e, int env0, int n, int nray, const float* d_pnt, const float* d_vec, const mjh_ray_options* opt,
                               float* d_dist, int* d_geomid) {
   ENG(e);
@@ -2237,18 +2261,12 @@ extern "C" int mjh_ray_device(mjh_engine* e, int env0, int n, int nray, const fl
   if (rc) return rc;
   mjh_ray_options o; mjh_ray_default_options(&o);
   if (opt) o = *opt;
-  const mjh_model* m = e->model;
   RayArgs A{};
   rc = ray_scene(e, env0, n, o.site >= 0, o.bodyexclude, o.flg_static, o.cutoff, &A.W, &A.T);
   if (rc) return rc;
   A.pnt = d_pnt; A.vec = d_vec; A.dist = d_dist; A.geomid = d_geomid;
   A.nray = nray; A.per_env = o.per_env ? 1 : 0;
-  A.site_body = -1;
-  if (o.site >= 0) {
-    A.site_body = m->site_bodyid[o.site];
-    for (int k = 0; k < 3; k++) A.site_pos[k] = (float)m->site_pos[3 * o.site + k];
-    for (int k = 0; k < 4; k++) A.site_quat[k] = (float)m->site_quat[4 * o.site + k];
-  }
+  site_frame(e->model, o.site, &A);
   HIPCHK(mjh_launch_ray(e->stream, A));
   return MJH_OK;
 }
@@ -2393,7 +2411,6 @@ extern "C" int mjh_scan_device(mjh_engine* e, int env0, int n, const mjh_scan_op
   if (rc) return rc;
   rc = scan_tables(e, o);
   if (rc) return rc;
-  const mjh_model* m = e->model;
   ScanArgs A{};
   rc = ray_scene(e, env0, n, o.site >= 0, o.bodyexclude, o.flg_static, o.cutoff, &A.W, &A.T);
   if (rc) return rc;
@@ -2401,12 +2418,7 @@ extern "C" int mjh_scan_device(mjh_engine* e, int env0, int n, const mjh_scan_op
   A.width = o.width; A.height = o.height; A.tw_log = scan_tile_shape(o.height); A.cull = o.cull ? 1 : 0;
   A.az_step = (float)std::fabs(o.azimuth_step);
   if (!(A.az_step >= std::fabs(o.azimuth_step))) A.az_step = std::nextafter(A.az_step, INFINITY);      // (rounded up: the half-span test may only err towards `no cone`)
-  A.site_body = -1;
-  if (o.site >= 0) {
-    A.site_body = m->site_bodyid[o.site];
-    for (int k = 0; k < 3; k++) A.site_pos[k] = (float)m->site_pos[3 * o.site + k];
-    for (int k = 0; k < 4; k++) A.site_quat[k] = (float)m->site_quat[4 * o.site + k];
-  }
+  site_frame(e->model, o.site, &A);
   HIPCHK(mjh_launch_scan(e->stream, A));
   return MJH_OK;
 }
@@ -2416,17 +2428,8 @@ extern "C" int mjh_scan(mjh_engine* e, int env0, int n, const mjh_scan_options* 
   if (opt) o = *opt;
   int rc = scan_check(e, env0, n, o, range);
   if (rc) return rc;
-  const size_t nout = (size_t)n * o.width * o.height;
-  rc = ray_io_reserve(e, 5 * nout);
-  if (rc) return rc;
-  float* const d_range = e->ray_io; int* const d_gid = (int*)(e->ray_io + nout); float* const d_pts = e->ray_io + 2 * nout;
-  rc = mjh_scan_device(e, env0, n, &o, d_range, geomid ? d_gid : nullptr, points ? d_pts : nullptr);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(range, d_range, nout * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-  if (geomid) HIPCHK(hipMemcpyAsync(geomid, d_gid, nout * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  if (points) HIPCHK(hipMemcpyAsync(points, d_pts, 3 * nout * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  return MJH_OK;
+  return scan_readback(e, (size_t)n * o.width * o.height, range, geomid, points,
+                       [&](float* d_range, int* d_geomid, float* d_points) { return mjh_scan_device(e, env0, n, &o, d_range, d_geomid, d_points); });
 }
 
 // ---- contact report (mjh_set_contact_report): the readers of what the step kernel's report stage left (step_kernel.h), and the per-body
@@ -2734,12 +2737,7 @@ extern "C" int mjh_heightscan_device(mjh_engine* e, int env0, int n, const mjh_h
   A.ox = (float)o.offset[0]; A.oy = (float)o.offset[1]; A.hx = (float)(0.5 * o.spacing[0]); A.hy = (float)(0.5 * o.spacing[1]);
   A.above = (float)o.above;
   A.rootid = o.exclude_tree ? e->hscan_root : nullptr; A.root_ex = o.exclude_tree ? m->body_rootid[o.bodyexclude] : -1;
-  A.site_body = -1;
-  if (o.site >= 0) {
-    A.site_body = m->site_bodyid[o.site];
-    for (int k = 0; k < 3; k++) A.site_pos[k] = (float)m->site_pos[3 * o.site + k];
-    for (int k = 0; k < 4; k++) A.site_quat[k] = (float)m->site_quat[4 * o.site + k];
-  }
+  site_frame(m, o.site, &A);
   HIPCHK(mjh_launch_heightscan(e->stream, A));
   return MJH_OK;
 }
@@ -2749,17 +2747,8 @@ extern "C" int mjh_heightscan(mjh_engine* e, int env0, int n, const mjh_heightsc
   if (opt) o = *opt;
   int rc = hscan_check(e, env0, n, o, range);
   if (rc) return rc;
-  const size_t nout = (size_t)n * o.width * o.height;
-  rc = ray_io_reserve(e, 5 * nout);
-  if (rc) return rc;
-  float* const d_range = e->ray_io; int* const d_gid = (int*)(e->ray_io + nout); float* const d_pts = e->ray_io + 2 * nout;
-  rc = mjh_heightscan_device(e, env0, n, &o, d_range, geomid ? d_gid : nullptr, points ? d_pts : nullptr);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(range, d_range, nout * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-  if (geomid) HIPCHK(hipMemcpyAsync(geomid, d_gid, nout * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  if (points) HIPCHK(hipMemcpyAsync(points, d_pts, 3 * nout * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  return MJH_OK;
+  return scan_readback(e, (size_t)n * o.width * o.height, range, geomid, points,
+                       [&](float* d_range, int* d_geomid, float* d_points) { return mjh_heightscan_device(e, env0, n, &o, d_range, d_geomid, d_points); });
 }
 
 // ---- RGB-D images (mjh_render / mjh_render_device, render.hip): the depth launch exactly as mjh_depth_device issues it — into the

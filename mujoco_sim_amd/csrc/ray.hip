@@ -62,8 +62,6 @@ __global__ __launch_bounds__(RAY_TILE) void mjh_ray_kernel(const RayArgs A) {
 
 hipError_t mjh_launch_ray(hipStream_t st, const RayArgs& A) {
   const long long ntile = ((long long)A.nray + RAY_TILE - 1) / RAY_TILE, blocks = ntile * (long long)A.W.n;
-  if (A.W.n <= 0 || A.nray <= 0 || blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-  if (A.T.mesh) hipLaunchKernelGGL(mjh_ray_kernel<true>, dim3((unsigned)blocks), dim3(RAY_TILE), 0, st, A);
-  else hipLaunchKernelGGL(mjh_ray_kernel<false>, dim3((unsigned)blocks), dim3(RAY_TILE), 0, st, A);
-  return hipGetLastError();
+  if (A.W.n <= 0 || A.nray <= 0) return hipErrorInvalidValue;
+  return RAY_LAUNCH_TRI(mjh_ray_kernel, A.T, blocks, st, A);
 }

@@ -10,13 +10,11 @@
 #include "../../include/mjhip.h"
 #include "dev_scan.h"
 
-static __device__ __forceinline__ float uniform(float x) { return ray_float(ray_uniform(ray_bits(x))); }
-
-// One workgroup (one wavefront) per (env, tile of TH x TW beams), one beam per lane: row lane >> tw_log, column lane & (TW - 1); the
-// shape is a launch argument (scan_tile_shape), the same for every wave.  Staging, compaction and the walk are depth.hip's: the env's
-// geom records are staged RAY_PASS geoms per pass, only the visible geoms whose bounding sphere touches the tile's cone reach LDS, in
-// ascending geom id (so ties break as in ray.hip).  Planes and height fields are never culled, and neither is anything in a tile
-// without a cone (scan_tile_cone).  cull = 0 skips the cone test only: the images are the same bits.
+// One workgroup (one wavefront) per (env, tile of TH x TW beams), one beam per lane: row lane >> tw_log, column lane & (TW - 1)
+// (dev_depth.h: tile_map); the shape is a launch argument (scan_tile_shape), the same for every wave.  The env's geom records are
+// staged RAY_PASS geoms per pass by ray_stage (dev_ray.h): only the visible geoms whose bounding sphere touches the tile's cone reach
+// LDS, compacted in ascending geom id.  Planes and height fields are never culled, and neither is anything in a tile without a cone
+// (scan_tile_cone).  cull = 0 skips the cone test only: the images are the same bits.
 // TRI and amdgpu_num_sgpr(96): as mjh_depth_kernel — the triangle walk's scalar registers on top of the cone, the scene's and the
 // tables' pointers would cost the instance with it a wave per SIMD; capped it keeps the 8 its LDS allows, without scratch (DESIGN.md
 // section 4f has the figures).
@@ -25,15 +23,11 @@ __global__ __launch_bounds__(RAY_TILE) __attribute__((amdgpu_num_sgpr(96))) void
   __shared__ float s_rec[RAY_PASS * RAY_REC];
   const RayScene& W = A.W;
   const int lane = (int)threadIdx.x;
-  const int tw_log = A.tw_log, TW = 1 << tw_log, TH = RAY_TILE >> tw_log;
-  const int tx = (A.width + TW - 1) >> tw_log, ty = (A.height + TH - 1) >> (6 - tw_log), ntile = tx * ty;
-  const int row = (int)blockIdx.x / ntile, tile = (int)blockIdx.x - row * ntile;
+  const int row = tile_row((int)blockIdx.x, A.width, A.height, A.tw_log);
   if (row >= W.n) return;
-  const int env = W.env0 + row;
-  const int trow = tile / tx, tcol = tile - trow * tx;
-  const int i0 = trow * TH, j0 = tcol << tw_log;
-  const int pi = i0 + (lane >> tw_log), pj = j0 + (lane & (TW - 1));
-  const bool live = pi < A.height && pj < A.width;
+  const TileMap tm = tile_map((int)blockIdx.x, row, lane, A.width, A.height, A.tw_log);
+  const int env = W.env0 + row, pi = tm.pi, pj = tm.pj;
+  const bool live = tm.live;
 
   // the sensor's world pose from its body's exported pose, once per env (wave-uniform); without a site the world frame
   float p[3] = {0.0f, 0.0f, 0.0f}, S[9] = {1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f};
@@ -48,7 +42,7 @@ __global__ __launch_bounds__(RAY_TILE) __attribute__((amdgpu_num_sgpr(96))) void
   const bool valid = vv > 0.0f && vv < 3.0e38f;      // (a non-finite pose sees nothing)
   // the tile's cone in the world frame (wave-uniform): the part of the tile inside the pattern
   float ac[3], axis[3], cosA, sinA;
-  const bool cone = scan_tile_cone(A.tab, A.width, A.height, i0, min(TH, A.height - i0), j0, min(TW, A.width - j0), A.az_step, ac, cosA, sinA);
+  const bool cone = scan_tile_cone(A.tab, A.width, A.height, tm.i0, tm.ni, tm.j0, tm.nj, A.az_step, ac, cosA, sinA);
 #pragma unroll
   for (int k = 0; k < 3; k++) axis[k] = S[3*k] * ac[0] + S[3*k+1] * ac[1] + S[3*k+2] * ac[2];
 
@@ -63,32 +57,14 @@ __global__ __launch_bounds__(RAY_TILE) __attribute__((amdgpu_num_sgpr(96))) void
 
   float best = -1.0f; int bestg = -1;
   for (int base = 0; base < W.ngeom; base += RAY_PASS) {
-    __syncthreads();
-    const int g = base + lane;
-    // stage geom g of this env: the verdict first (type, body, bounding sphere), then only a survivor's record is read and stored
-    int4 gi = make_int4(-1, 0, 0, 0);
-    float c[3] = {0.0f, 0.0f, 0.0f}, s[3] = {0.0f, 0.0f, 0.0f}, rb = 0.0f;
-    bool keep = false;
-    if (g < W.ngeom) {
-      gi = W.ginfo[g];
-      const float* gp = W.gpos + ((size_t)row * W.ngeom + g) * 3;
-#pragma unroll
-      for (int k = 0; k < 3; k++) c[k] = gp[k];
-#pragma unroll
-      for (int k = 0; k < 3; k++) s[k] = gsize[3*g + k];
-      keep = ray_verdict<TRI>(W, gi, s, slotmask, rb, &A.T) >= 0;
-      if (keep && cull && gi.x >= MJH_GEOM_SPHERE) {      // planes and height fields are never culled
+    const int cnt = ray_stage<TRI>(W, &A.T, s_rec, row, base, lane, slotmask, gsize, [=](bool keep, const int4 gi, const float* c, float rb) {
+      if (keep && cull && ray_cullable(gi)) {
         const float rel[3] = {c[0] - p[0], c[1] - p[1], c[2] - p[2]};
         keep = depth_cone_keep(axis, cosA, sinA, rel, rb);
       }
-    }
-    const unsigned long long kept = __ballot(keep);
-    if (keep) {      // the survivors in ascending geom id: record `number of survivors in the lanes below`
-      const int slot = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(kept >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)kept, 0u));
-      ray_store(s_rec + slot * RAY_REC, c, W.gmat + ((size_t)row * W.ngeom + g) * 9, s, rb, gi.x, gi.w, g);
-    }
-    __syncthreads();
-    ray_walk<false, TRI>(W, s_rec, __popcll(kept), p, v, vv, valid, best, bestg, &A.T);
+      return keep;
+    });
+    ray_walk<false, TRI>(W, s_rec, cnt, p, v, vv, valid, best, bestg, &A.T);
   }
   // the ray parameter is in units of |v| (1 up to rounding): the range is the Euclidean distance from the sensor origin
   best *= sqrtf(vv);
@@ -108,10 +84,5 @@ __global__ __launch_bounds__(RAY_TILE) __attribute__((amdgpu_num_sgpr(96))) void
 
 hipError_t mjh_launch_scan(hipStream_t st, const ScanArgs& A) {
   if (A.W.n <= 0 || A.width <= 0 || A.height <= 0 || A.tw_log < 3 || A.tw_log > 6 || !A.tab || !A.range) return hipErrorInvalidValue;
-  const int TW = 1 << A.tw_log, TH = RAY_TILE >> A.tw_log;
-  const long long tx = (A.width + TW - 1) / TW, ty = (A.height + TH - 1) / TH, blocks = tx * ty * (long long)A.W.n;
-  if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-  if (A.T.mesh) hipLaunchKernelGGL(mjh_scan_kernel<true>, dim3((unsigned)blocks), dim3(RAY_TILE), 0, st, A);
-  else hipLaunchKernelGGL(mjh_scan_kernel<false>, dim3((unsigned)blocks), dim3(RAY_TILE), 0, st, A);
-  return hipGetLastError();
+  return RAY_LAUNCH_TRI(mjh_scan_kernel, A.T, tile_blocks(A.width, A.height, A.tw_log, A.W.n), st, A);
 }

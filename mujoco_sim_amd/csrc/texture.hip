@@ -17,13 +17,11 @@ __global__ __launch_bounds__(RAY_TILE) void mjh_texture_kernel(const TextureArgs
   const DepthArgs& D = A.D;
   const RayScene& W = D.W;
   const int lane = (int)threadIdx.x;
-  const int tx = (D.width + DEPTH_TILE - 1) / DEPTH_TILE, ty = (D.height + DEPTH_TILE - 1) / DEPTH_TILE, ntile = tx * ty;
-  const int row = (int)blockIdx.x / ntile, tile = (int)blockIdx.x - row * ntile;
+  const int row = tile_row((int)blockIdx.x, D.width, D.height, DEPTH_TILE_LOG);
   if (row >= W.n) return;
-  const int env = W.env0 + row;
-  const int trow = tile / tx, tcol = tile - trow * tx;
-  const int pi = trow * DEPTH_TILE + (lane >> 3), pj = tcol * DEPTH_TILE + (lane & 7);
-  const bool live = pi < D.height && pj < D.width;
+  const TileMap tm = tile_map((int)blockIdx.x, row, lane, D.width, D.height, DEPTH_TILE_LOG);
+  const int env = W.env0 + row, pi = tm.pi, pj = tm.pj;
+  const bool live = tm.live;
 
   float p[3], S[9];
   RAY_FRAME(W.xpos + ((size_t)row * W.nbody + D.cam_body) * 3, W.xquat + ((size_t)row * W.nbody + D.cam_body) * 4, D.cam_pos, D.cam_quat, p, S);
@@ -73,8 +71,5 @@ __global__ __launch_bounds__(RAY_TILE) void mjh_texture_kernel(const TextureArgs
 hipError_t mjh_launch_texture(hipStream_t st, const TextureArgs& A) {
   const DepthArgs& D = A.D;
   if (D.W.n <= 0 || D.width <= 0 || D.height <= 0 || !D.depth || !D.geomid || !A.rec || !A.texels || A.ntexdata <= 0 || !A.out) return hipErrorInvalidValue;
-  const long long tx = (D.width + DEPTH_TILE - 1) / DEPTH_TILE, ty = (D.height + DEPTH_TILE - 1) / DEPTH_TILE, blocks = tx * ty * (long long)D.W.n;
-  if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(mjh_texture_kernel, dim3((unsigned)blocks), dim3(RAY_TILE), 0, st, A);
-  return hipGetLastError();
+  return ray_launch(mjh_texture_kernel, tile_blocks(D.width, D.height, DEPTH_TILE_LOG, D.W.n), st, A);
 }

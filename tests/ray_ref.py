@@ -668,6 +668,15 @@ def many_spheres_spec(n=70, seed=41):
     return spec
 
 
+def pass_edge_spec(ngeom, seed=41):
+    """many_spheres_spec() with exactly `ngeom` geoms, every one visible, the last sphere on a free body (a model needs a moving one):
+    65 geoms leave the second staging pass of the kernels that trace per tile a single candidate, 130 reach a third pass.
+    -> (spec, position of the last sphere)"""
+    spec = many_spheres_spec(n=ngeom - 1, seed=seed)
+    spec[-1] = dict(spec[-1], free=True)
+    return spec, spec[-1]["pos"]
+
+
 def many_spheres_rays(scene, nray=96, seed=43):
     return make_rays(seed, scene, nray, (-3.0, -2.5, 0.05), (3.0, 2.5, 3.0))
 

@@ -247,6 +247,27 @@ def test_more_geoms_than_one_staging_pass(spheres, width, height):
     assert (gid[0] >= 64).any() and ((gid[0] >= 0) & (gid[0] < 64)).any(), "geoms of both staging passes are seen"
 
 
+@pytest.mark.parametrize("ngeom", [65, 130])
+def test_staging_pass_edges(lib, ngeom):
+    """65 geoms: the second staging pass holds a single candidate; 130: a third pass follows a full second one.  The camera stands over
+    the last sphere; 9 x 8 pixels: tiles partial in both directions"""
+    spec, last = rr.pass_edge_spec(ngeom)
+    b = lib.mjh_builder_create()
+    set_opt(lib, b, gravity=[0, 0, 0])
+    add_spec(lib, b, spec)
+    add_camera(lib, b, b"over", 0, ((last[0] + 0.3, last[1] - 0.8, 3.0), (last[0] - 0.25, last[1] - 0.15, 0.5), 45.0))
+    m = compile_model(lib, b)
+    assert m.ngeom == ngeom
+    e = ms.Engine(m, NENV)
+    depth, gid = render(e, "over", 9, 8)      # (cull 0 and cull 1: the same bits)
+    for env in range(1, NENV):
+        assert np.array_equal(depth[env], depth[0]) and np.array_equal(gid[env], gid[0])
+    check(f"{ngeom} geoms 9x8", depth[0], gid[0], device_scene(e, m, 0), camera_rays(e, m, 0, 0, 9, 8))
+    assert (gid[0] == ngeom - 1).any(), "the last geom, in the last pass, is seen"
+    assert all(((gid[0] >= 64 * p) & (gid[0] < 64 * (p + 1))).any() for p in range((ngeom + 63) // 64)), "geoms of every staging pass are seen"
+    e.close()
+
+
 @pytest.fixture(scope="module")
 def tetra(lib):
     spec = rm.tetra_field_spec()

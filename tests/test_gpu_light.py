@@ -19,6 +19,7 @@ import ray_mesh_ref as rm
 import ray_ref as rr
 import render_check as rc
 import render_ref as rf
+from helpers import set_opt
 from light_check import NENV, check_light
 from mujoco_sim_amd import capi
 from mujoco_sim_amd.engine import MjhError
@@ -157,6 +158,57 @@ def test_many_spheres_two_passes(lib):
     assert (sg >= 64).any() and ((sg >= 0) & (sg < 64)).any(), "the nearest occluder lies in either staging pass"
     for env in range(1, NENV):
         assert np.array_equal(out[3][env], out[3][0])
+    e.close()
+
+
+EDGE_SUN = {65: (0.1, 1.0, -0.3), 130: (0.1, 1.0, -0.4)}      # low suns under which shadow rays meet geoms of the first and of the last pass
+
+
+def edge_occluders(spec, rays, L, centre, cast, keep):
+    """per light: (a kept cast-shadow pixel whose shadow ray a geom of the FIRST staging pass blocks, one that only geoms of the LAST
+    pass block), from the fp64 reference cast against the geoms of one pass at a time"""
+    d, g, n, _ = centre
+    npass = (len(spec) + 63) // 64
+    out = []
+    for l in range(len(L)):
+        k = cast[l] & keep
+        o = rays[0][k] + d[k, None] * rays[1][k] + lc.BIAS * n[k]
+        v = np.tile(-np.asarray(L[l]["dir"]), (int(k.sum()), 1))
+        hit = np.array([rm.cast(o, v, rr.scene_from_spec(spec[64 * p:64 * (p + 1)]))[1] >= 0 for p in range(npass)])
+        out.append((bool(hit[0].any()), bool((hit[-1] & ~hit[:-1].any(axis=0)).any())))
+    return out
+
+
+@pytest.mark.parametrize("ngeom", [65, 130])
+def test_staging_pass_edges(lib, ngeom):
+    """65 geoms: the second staging pass holds a single candidate; 130: a third pass follows a full second one.  A low sun over the
+    last sphere, 9 x 8 pixels (tiles partial in both directions): some shadow rays are blocked by a geom of the first pass (those lanes
+    stop walking there), some only by a geom of the last one, and the lit pixels walk every pass.  NOT pinned here: that a whole wave leaves
+    the pass loop through the wave-uniform `break` (`__ballot(walking) == 0`) before the last pass — that takes a tile whose every walking
+    lane is blocked early, which these 72 pixels do not guarantee"""
+    spec, last = rr.pass_edge_spec(ngeom)
+    b = lib.mjh_builder_create()
+    set_opt(lib, b, gravity=[0, 0, 0])
+    rc.add_spec(lib, b, spec, rc.palette(len(spec), seed=6))
+    rc.add_camera(lib, b, b"over", 0, ((last[0] + 0.3, last[1] - 0.8, 3.0), (last[0] - 0.25, last[1] - 0.15, 0.5), 45.0))
+    lc.add_light(lib, b, 0, dict(lc.LOW_SUN, dir=EDGE_SUN[ngeom]))
+    m = rc.compile_model(lib, b)
+    assert m.ngeom == ngeom and m.nlight == 1
+    e = engine(m)
+    out = e.render("over", 9, 8)
+    e.light_options = dict(cull=0)
+    assert same(e.render("over", 9, 8), out), "cull 0 and 1 give equal bytes"
+    e.light_options = dict(cull=1)
+    for env in range(1, NENV):
+        assert np.array_equal(out[3][env], out[3][0])
+    check_env(f"{ngeom} geoms 9x8", e, m, "over", 9, 8, 0, out)
+    rays = rc.camera_rays(e, m, 0, 0, 9, 8); L = lc.device_lights(e, m, 0)
+    centre, term, cast, keep, _ = lc.kept_pixels(f"{ngeom} geoms 9x8", rc.device_scene(e, m, 0), rays, L)
+    occ = edge_occluders(spec, rays, L, centre, cast, keep)
+    print(f"{ngeom} geoms: per light (blocked by the first pass, blocked by the last pass alone) {occ}")
+    assert occ[0] == (True, True)
+    lit = keep & (centre[1] >= 0) & ~cast[0] & (term.max(axis=(0, 2)) > 0.05)
+    assert lit.sum() >= 8, "lit pixels: their lanes walk every pass"
     e.close()
 
 

@@ -343,6 +343,28 @@ def test_more_geoms_than_one_staging_pass(lib):
     e.close()
 
 
+@pytest.mark.parametrize("ngeom", [65, 130])
+def test_staging_pass_edges(lib, ngeom):
+    """65 geoms: the second staging pass holds a single candidate; 130: a third pass follows a full second one.  The sensor hangs over
+    the last sphere and looks down; 5 rows of 9 beams: tiles partial in both directions"""
+    spec, last = rr.pass_edge_spec(ngeom)
+    pattern = (9, 5, -np.pi, 2 * np.pi / 9, (-85.0 * DEG, 9.0 * DEG))
+    b = lib.mjh_builder_create()
+    set_opt(lib, b, gravity=[0, 0, 0])
+    add_spec(lib, b, spec)
+    add_site(lib, b, b"lidar", 0, ((last[0] - 0.2, last[1] - 0.1, 1.7), yaw(0.3)))
+    m = compile_model(lib, b)
+    assert m.ngeom == ngeom
+    e = ms.Engine(m, NENV)
+    r, g = scan(e, "lidar", pattern)      # (cull 0 and cull 1: the same bits)
+    for env in range(1, NENV):
+        assert np.array_equal(bits(r[env]), bits(r[0])) and np.array_equal(g[env], g[0])
+    check(f"{ngeom} geoms 5x9", r[0], g[0], device_scene(e, m, 0), sensor_rays(e, m, 0, 0, pattern))
+    assert (g[0] == ngeom - 1).any(), "the last geom, in the last pass, is seen"
+    assert all(((g[0] >= 64 * p) & (g[0] < 64 * (p + 1))).any() for p in range((ngeom + 63) // 64)), "geoms of every staging pass are seen"
+    e.close()
+
+
 def test_tetrahedron_field_in_mesh_mode_1(lib):
     m = tetra_model(lib)
     assert m.ngeom == 107 and (m.array("geom_type") == rr.MESH).sum() == 70

@@ -6,6 +6,11 @@ mesh model in mesh modes 0 and 1, the tetrahedron field in mesh mode 1, more tha
 cull on and off and range on and off.  Mesh surface 1 (the meshes' own triangles) for the mesh model and the tetrahedron field, through
 both calls.  For every camera and size mjh_render's normal and rgba images with range on and off, and the models of the render tests
 (tests/render_check.py): the height field from the side and from below (its base and walls), the meshes as hulls and as triangles.
+The other kernels that trace per tile, with the builders of their GPU tests: mjh_scan (range, geom id, points) on the primitives from the
+world frame and from a site on a free ball, in every tile shape, with an elevation table, a cutoff, cull on and off, over more than 64
+spheres and through mesh surface 1; mjh_heightscan at 1 x 1, 9 x 5 and 17 x 16 in the three alignments with exclude_tree and the cull
+on and off, over a plane, the primitives, the height field, more than 64 spheres and mesh surface 1; mjh_render with lighting 1 for the
+models of tests/light_check.py (spot, directional and positional lights), shadows and the light cull on and off, once with texturing 1.
 
     python tools/ray_depth_dump.py OUT.npz
     python tools/ray_depth_dump.py --compare A.npz B.npz      (exit status 1 and the first array that differs, if any)
@@ -195,6 +200,104 @@ def dump(path):
     e = ms.Engine(td.compile_model(lib, b), NENV)
     rays("spheres/world", e, *rr.many_spheres_rays(rr.scene_from_spec(spec)))
     images("spheres/above", e, "above")
+    e.close()
+
+    # ---- the kernels that trace per tile besides depth: lidar scans, height scans, lit (and textured) renders
+    import heightscan_ref as hr
+    import light_check as lc
+    import scan_ref as sr
+    import test_gpu_heightscan as th
+    import test_gpu_scan as ts
+    import texture_check as tc
+
+    def scans(tag, e, site, patterns, **kw):
+        for name, pattern in patterns:
+            for cull in (0, 1):
+                r, g, pts = e.scan(site, **sr.scan_kwargs(pattern), cull=cull, points=True, **kw)
+                for k, a in (("range", r), ("geomid", g), ("points", pts)):
+                    out[f"{tag}/{name}/cull{cull}/{k}"] = a
+
+    def hscans(tag, e, site, grids, aligns=hr.ALIGNS, **kw):
+        for w, h in grids:
+            for align in aligns:
+                for cull in (0, 1):
+                    r, g, pts = e.height_scan(site, **hr.kwargs((w, h, (0.11, 0.09), (0.05, -0.03), 0.5)), align=align, cull=cull, points=True, **kw)
+                    for k, a in (("range", r), ("geomid", g), ("points", pts)):
+                        out[f"{tag}/{w}x{h}/{align}/cull{cull}/{k}"] = a
+
+    def lit(tag, e, cam, sizes=SIZES):
+        for w, h in sizes:
+            for shadows in (0, 1):
+                for cull in (0, 1):
+                    e.light_options = dict(shadows=shadows, cull=cull)
+                    for k, a in zip(("depth", "geomid", "normal", "rgba"), e.render(cam, w, h)):
+                        out[f"{tag}/{w}x{h}/shadows{shadows}/cull{cull}/{k}"] = a
+
+    # every tile shape scan_tile_shape returns (1 x 64, 2 x 32, 4 x 16, 8 x 8), partial tiles in both directions, an elevation table
+    PATTERNS = [("360x1", (360, 1, -np.pi, 2 * np.pi / 360, (0.0, 0.0))), ("40x2", (40, 2, -1.0, 0.05, (-0.3, 0.2))), ("20x3", (20, 3, 0.4, 0.06, (-0.5, 0.2))),
+                ("33x5", (33, 5, -1.9, 0.11, (-0.6, 0.2))), ("70x16", (70, 16, -np.pi, 2 * np.pi / 70, (-0.9, 0.1))), ("table 9x70", sr.PATTERNS["table 9x70"])]
+    m = ts.prim_model(lib, rig=True)
+    e = ms.Engine(m, NENV)
+    e.set_state(qpos=ts.rig_qpos(m), qvel=np.zeros((NENV, m.nv)))
+    e.forward()
+    rig = m.name2id(0, "rig")
+    scans("scan/world", e, None, PATTERNS)
+    scans("scan/site", e, "head", PATTERNS, bodyexclude=rig)
+    scans("scan/site_cutoff", e, "head", PATTERNS[3:4], bodyexclude=rig, cutoff=1.5)
+    e.close()
+    e = ms.Engine(ts.spheres_model(lib), NENV)
+    scans("scan/spheres", e, "lidar", [("128x8", ts.SPHERES_PATTERN)])
+    e.close()
+    e = ms.Engine(ts.tri_model(lib), NENV)
+    e.ray_mesh_mode = 1; e.ray_mesh_surface = 1
+    scans("scan/surface1", e, "scanner", [("96x8", ts.TRI_PATTERN)])
+    hscans("hscan/surface1", e, "scanner", [(17, 16)], aligns=("yaw",))
+    e.close()
+
+    GRIDS = [(1, 1), (9, 5), (17, 16)]
+    m = th.tree_model(lib)      # a floor (a plane), a base with an arm, another body: exclude_tree hides the first two
+    e = ms.Engine(m, NENV)
+    q = np.tile(m.array("qpos0"), (NENV, 1))
+    q[:, int(m.array("jnt_qposadr")[m.name2id(1, "elbow")])] = [0.0, 0.3, -0.4, 0.7]
+    e.set_state(qpos=q, qvel=np.zeros((NENV, m.nv))); e.forward()
+    base = m.name2id(0, "base")
+    for tree in (0, 1):
+        hscans(f"hscan/plane/tree{tree}", e, "head", GRIDS, bodyexclude=base, exclude_tree=tree)
+    e.close()
+    m = th.prim_model(lib, rig=True)
+    e = ms.Engine(m, NENV)
+    e.set_state(qpos=th.rig_qpos(m), qvel=np.zeros((NENV, m.nv))); e.forward()
+    for tree in (0, 1):
+        hscans(f"hscan/prim/tree{tree}", e, "head", GRIDS, bodyexclude=m.name2id(0, "rig"), exclude_tree=tree)
+    e.close()
+    e = ms.Engine(th.hfield_model(lib, (rr.HF_NROW, rr.HF_NCOL, np.array(rr.HF_SIZE), rr.HF_ELEV), rr.HF_POS, rr.HF_QUAT, th.HFIELD_SENSOR), NENV)
+    hscans("hscan/hfield", e, "scanner", GRIDS)
+    e.close()
+    e = ms.Engine(th.spheres_model(lib), NENV)
+    hscans("hscan/spheres", e, "scanner", GRIDS)
+    e.close()
+
+    m = lc.prim_model(lib, lights=(lc.SPOT, lc.SUN, lc.LOW_SPOT))      # a spot, a directional and a positional light inside the scene
+    e = ms.Engine(m, NENV)
+    e.render_lighting = 1
+    lit("light/prim/front", e, "front")
+    lit("light/prim/side", e, "side", sizes=[(9, 8)])
+    e.close()
+    e = ms.Engine(lc.spheres_model(lib), NENV)
+    e.render_lighting = 1
+    lit("light/spheres", e, "above")
+    e.close()
+    e = ms.Engine(lc.hfield_model(lib), NENV)
+    e.render_lighting = 1
+    lit("light/hfield", e, "cam", sizes=[(9, 8), (30, 20)])
+    e.close()
+    e = ms.Engine(lc.meshes_model(lib)[0], NENV)
+    e.render_lighting = 1; e.ray_mesh_mode = 1; e.ray_mesh_surface = 1
+    lit("light/surface1", e, "cam", sizes=[(9, 8), (24, 16)])
+    e.close()
+    e = ms.Engine(tc.prim_model(lib, lights=(lc.SPOT, lc.SUN)), NENV)
+    e.render_lighting = 1; e.render_texturing = 1
+    lit("light/textured", e, "front")
     e.close()
 
     hits = {k: float((a >= 0).mean()) for k, a in out.items() if k.endswith("geomid")}
