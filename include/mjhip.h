@@ -948,6 +948,33 @@ enum { MJH_FRAME_LOCAL = 1 };
 typedef struct mjh_frame { int objtype, id, reftype, refid, flags; } mjh_frame;
 int mjh_frame_state_device(mjh_engine*, int env0, int n, int nframe, const mjh_frame* frames, void* d_state, void* d_jac);
 int mjh_frame_state(mjh_engine*, int env0, int n, int nframe, const mjh_frame* frames, double* state, double* jac);
+/* ------------------------------------------------- frame accelerations: IMU accelerometer readings and Jdot qvel of bodies and sites
+ * Per env and frame, with p the frame's world origin carried by its body and J(p) the Jacobian of mjh_frame_state:
+ *   acc  = linacc[3], angacc[3] = J(p) qacc + Jdot(p) qvel: the classical acceleration d2p/dt2 of the point and the angular acceleration of
+ *          the body, in world axes.  flags & MJH_FRAME_PROPER subtracts the model's gravity from linacc (a body at rest reads -g, a body
+ *          in free fall 0: MuJoCo's cacc[world] = -gravity convention; nothing is subtracted with MJH_DSBL_GRAVITY); flags &
+ *          MJH_FRAME_LOCAL then rotates both vectors into the frame's own axes.  LOCAL | PROPER on a site is MuJoCo's <accelerometer>
+ *          (LOCAL on mjh_frame_state stays the <gyro> and the <velocimeter>).
+ *   bias = Jdot(p) qvel, the linear part first, without the qacc term: always in world axes at the frame's world origin whatever the flags
+ *          say, as the Jacobian output of mjh_frame_state is — with that Jacobian what a task-space controller needs.  Optional.
+ * refid must be -1: acceleration has no ref-relative form here.  MJH_FRAME_PROPER is valid in these two calls only.
+ * The call reads the envs' present qpos and qvel and the engine's qacc array, that is the qacc of the last solve (mjh_get_field "qacc");
+ * the warm start of mjh_set_state writes the same array.  Timing: after mjh_forward the three are one consistent state and the result is
+ * exact; after mjh_step pose and velocity are at the new time and qacc is that of the step just taken — MuJoCo's own one-step staleness of
+ * sensordata, first-order accurate in the timestep.  Nothing of the envs' state, statistics or time is written.
+ * A mocap body and the world report zero acceleration (-g with PROPER) and a zero bias; bodies of inactive slots are reported as they are.
+ * One position-stage launch of the env range and one launch of mjh_frame_accel_kernel (csrc/frame_acc.hip) on the engine's stream behind
+ * the steps queued so far, as mjh_frame_state; the frame table (kept apart from mjh_frame_state's: alternating calls upload nothing) is
+ * uploaded only when it differs from the last accel call's.  The order of the additions is fixed per env and frame: a result does not
+ * depend on nenv, env0, n, the other frames of the call or on whether the bias was asked for (bitwise).  Device form: d_acc float
+ * [n][nframe][6], d_bias float [n][nframe][6] or NULL, no synchronisation.  Host form: doubles, synchronises; bias may be NULL.
+ * An env range out of bounds, nframe <= 0, an objtype other than 0 / 1, an id outside [0, nbody) / [0, nsite), refid >= 0 (or < -1), a
+ * flag outside LOCAL | PROPER, a NULL frames / acc pointer, or n * nframe * 6 beyond 2^30 return MJH_ERR_ARG and launch nothing; an nv
+ * beyond 1092 (the kernel's LDS stage of 15 words per dof within the 64 KiB a launch gets without raising its dynamic-LDS limit)
+ * MJH_ERR_CAPACITY.  Not forwarded by mjh_group, not part of the pinned mirror. */
+enum { MJH_FRAME_PROPER = 2 };   /* beside MJH_FRAME_LOCAL = 1; valid in the two calls below only */
+int mjh_frame_accel_device(mjh_engine*, int env0, int n, int nframe, const mjh_frame* frames, void* d_acc, void* d_bias);
+int mjh_frame_accel(mjh_engine*, int env0, int n, int nframe, const mjh_frame* frames, double* acc, double* bias);
 int mjh_set_cohorts(mjh_engine*, int n);
 int mjh_get_cohorts(const mjh_engine*);
 /* mjh_step(e, n) of an articulated model in the LDS-resident layout runs up to `n` steps per launch and cohort with the environment's

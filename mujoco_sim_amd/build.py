@@ -27,6 +27,7 @@ SOURCES = {
     "heightscan.hip": ["dev_heightscan.h", "dev_scan.h", "dev_depth.h", "dev_ray.h", "ray_bvh.h", API],
     "contact.hip": ["dev_contact.h", API],
     "frame.hip": ["dev_frame.h", "dev_math.h", API],
+    "frame_acc.hip": ["dev_frame.h", "dev_math.h", API],
     "control.hip": ["dev_control.h", "dev_types.h", API],
     "render.hip": ["dev_render.h", "dev_depth.h", "dev_ray.h", "ray_bvh.h", API],
     "light.hip": ["dev_light.h", "dev_render.h", "dev_depth.h", "dev_ray.h", "ray_bvh.h", API],

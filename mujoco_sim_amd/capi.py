@@ -179,6 +179,8 @@ class HeightScanOptions(C.Structure):
 class Frame(C.Structure):
     _fields_ = [("objtype", C.c_int), ("id", C.c_int), ("reftype", C.c_int), ("refid", C.c_int), ("flags", C.c_int)]
 
+MJH_FRAME_LOCAL, MJH_FRAME_PROPER = 1, 2   # mjh_frame.flags (PROPER: mjh_frame_accel only)
+
 class LightOptions(C.Structure):
     _fields_ = [("shadows", C.c_int), ("cull", C.c_int), ("bias", C.c_float)]
 
@@ -338,6 +340,8 @@ SYMBOLS = [
     ("mjh_body_contact_force", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, c_int_p, c_int_p, c_double_p, c_int_p]),
     ("mjh_frame_state_device", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
     ("mjh_frame_state", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, c_double_p, c_double_p]),
+    ("mjh_frame_accel_device", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
+    ("mjh_frame_accel", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, c_double_p, c_double_p]),
     ("mjh_set_cmd_device", C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
     ("mjh_set_pd_target_device", C.c_int, [_vp, C.c_int, C.c_int, _vp]),
     ("mjh_set_xfrc_applied_device", C.c_int, [_vp, C.c_int, C.c_int, _vp]),

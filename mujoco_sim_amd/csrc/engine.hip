@@ -158,8 +158,13 @@ struct mjh_engine {
   // engine's other allocations); the frame table of the last call on the device — the pinned host buffer the upload is issued from, the event
   // that marks the upload's end — and the frames it holds (a call with the same ones uploads nothing); staging of the host form
   bool frame_ready = false; FrameModel frame_model{};
-  FrameRec* frame_tab = nullptr; FrameRec* frame_host = nullptr; int frame_cap = 0; hipEvent_t frame_up = nullptr; std::vector<int> frame_have;
+  struct FrameTable { FrameRec* tab = nullptr; FrameRec* host = nullptr; int cap = 0; hipEvent_t up = nullptr; std::vector<int> have; };
+  FrameTable frame_tab;
   float* frame_io = nullptr; size_t frame_io_floats = 0;
+  // frame accelerations (mjh_frame_accel / mjh_frame_accel_device, frame_acc.hip): the per-model tables above; a last-call frame table of
+  // their own, so that alternating state and acceleration calls upload nothing; staging of the host form
+  FrameTable facc_tab;
+  float* facc_io = nullptr; size_t facc_io_floats = 0;
   // mjh_reset with an id list (control.hip): the ids of a call go through a ring of pinned slots, each fenced by an event like the slots of
   // mjh_set_cmd, into one device buffer (rewritten in stream order); rid_cap ints per slot, grown to the longest list seen
   int* rid_host = nullptr; int* rid_dev = nullptr; size_t rid_cap = 0; hipEvent_t rid_ev[MJH_IO_SLOTS] = {}; bool rid_used[MJH_IO_SLOTS] = {}; unsigned rid_next = 0;
@@ -863,10 +868,13 @@ extern "C" void mjh_destroy(mjh_engine* e) {
   if (e->csel_host) (void)hipHostFree(e->csel_host);
   if (e->csel_up) (void)hipEventDestroy(e->csel_up);
   if (e->csel_io) (void)hipFree(e->csel_io);
-  if (e->frame_tab) (void)hipFree(e->frame_tab);
-  if (e->frame_host) (void)hipHostFree(e->frame_host);
-  if (e->frame_up) (void)hipEventDestroy(e->frame_up);
+  for (mjh_engine::FrameTable* T : {&e->frame_tab, &e->facc_tab}) {
+    if (T->tab) (void)hipFree(T->tab);
+    if (T->host) (void)hipHostFree(T->host);
+    if (T->up) (void)hipEventDestroy(T->up);
+  }
   if (e->frame_io) (void)hipFree(e->frame_io);
+  if (e->facc_io) (void)hipFree(e->facc_io);
   if (e->rid_host) (void)hipHostFree(e->rid_host);
   if (e->rid_dev) (void)hipFree(e->rid_dev);
   for (int k = 0; k < MJH_IO_SLOTS; k++) if (e->rid_ev[k]) (void)hipEventDestroy(e->rid_ev[k]);
@@ -2556,25 +2564,30 @@ extern "C" int mjh_body_contact_force(mjh_engine* e, int env0, int n, int nsel, 
 // when it is not the last call's, the position-stage launch with the body poses (as fk_export issues it), then mjh_frame_state_kernel on the
 // same stream.  Nothing of the envs' state, statistics or time is written.
 // argument checks shared by both entry points: nothing is launched when one fails
-static int frame_check(const mjh_engine* e, int env0, int n, int nframe, const mjh_frame* frames, const void* state, bool jac) {
+// (accel: the rules of mjh_frame_accel — words = FRA_OUT per frame, MJH_FRAME_PROPER allowed, no ref, the LDS stage of FRA_STAGE words per dof)
+static int frame_check(const mjh_engine* e, int env0, int n, int nframe, const mjh_frame* frames, const void* state, bool jac, bool accel = false) {
   const mjh_model* m = e->model;
-  if (env0 < 0 || n <= 0 || env0 + n > e->nenv) { mjh_set_error("mjh_frame_state: env range out of bounds"); return MJH_ERR_ARG; }
-  if (nframe <= 0 || !frames || !state) { mjh_set_error("mjh_frame_state: no frames or null pointer"); return MJH_ERR_ARG; }
-  if ((long long)n * nframe * FR_STATE > (1ll << 30)) { mjh_set_error("mjh_frame_state: n * nframe too large"); return MJH_ERR_ARG; }
-  if (jac && (long long)n * nframe * 6 * (long long)m->nv > (1ll << 30)) { mjh_set_error("mjh_frame_state: n * nframe * 6 * nv beyond 2^30"); return MJH_ERR_ARG; }
+  const char* const who = accel ? "mjh_frame_accel" : "mjh_frame_state";
+  const auto fail = [who](const char* what, int rc) { mjh_set_error(std::string(who) + what); return rc; };
+  if (env0 < 0 || n <= 0 || env0 + n > e->nenv) return fail(": env range out of bounds", MJH_ERR_ARG);
+  if (nframe <= 0 || !frames || !state) return fail(": no frames or null pointer", MJH_ERR_ARG);
+  if ((long long)n * nframe * (accel ? FRA_OUT : FR_STATE) > (1ll << 30)) return fail(": n * nframe too large", MJH_ERR_ARG);
+  if (jac && (long long)n * nframe * 6 * (long long)m->nv > (1ll << 30)) return fail(": n * nframe * 6 * nv beyond 2^30", MJH_ERR_ARG);
+  const int known = accel ? (MJH_FRAME_LOCAL | MJH_FRAME_PROPER) : MJH_FRAME_LOCAL;
   for (int f = 0; f < nframe; f++) {
     const mjh_frame& F = frames[f];
-    if (F.objtype != MJH_FRAME_BODY && F.objtype != MJH_FRAME_SITE) { mjh_set_error("mjh_frame_state: objtype is neither MJH_FRAME_BODY nor MJH_FRAME_SITE"); return MJH_ERR_ARG; }
-    if (F.id < 0 || F.id >= (F.objtype == MJH_FRAME_SITE ? m->nsite : m->nbody)) { mjh_set_error("mjh_frame_state: frame id out of range"); return MJH_ERR_ARG; }
-    if (F.flags & ~MJH_FRAME_LOCAL) { mjh_set_error("mjh_frame_state: unknown flag"); return MJH_ERR_ARG; }
-    if (F.refid < -1) { mjh_set_error("mjh_frame_state: bad ref"); return MJH_ERR_ARG; }
+    if (F.objtype != MJH_FRAME_BODY && F.objtype != MJH_FRAME_SITE) return fail(": objtype is neither MJH_FRAME_BODY nor MJH_FRAME_SITE", MJH_ERR_ARG);
+    if (F.id < 0 || F.id >= (F.objtype == MJH_FRAME_SITE ? m->nsite : m->nbody)) return fail(": frame id out of range", MJH_ERR_ARG);
+    if (F.flags & ~known) return fail(": unknown flag", MJH_ERR_ARG);
+    if (F.refid < -1) return fail(": bad ref", MJH_ERR_ARG);
     if (F.refid >= 0) {
-      if (F.reftype != MJH_FRAME_BODY && F.reftype != MJH_FRAME_SITE) { mjh_set_error("mjh_frame_state: reftype is neither MJH_FRAME_BODY nor MJH_FRAME_SITE"); return MJH_ERR_ARG; }
-      if (F.refid >= (F.reftype == MJH_FRAME_SITE ? m->nsite : m->nbody)) { mjh_set_error("mjh_frame_state: ref id out of range"); return MJH_ERR_ARG; }
-      if (F.flags & MJH_FRAME_LOCAL) { mjh_set_error("mjh_frame_state: MJH_FRAME_LOCAL together with a ref"); return MJH_ERR_ARG; }
+      if (accel) return fail(": refid must be -1 (accelerations have no ref-relative form)", MJH_ERR_ARG);
+      if (F.reftype != MJH_FRAME_BODY && F.reftype != MJH_FRAME_SITE) return fail(": reftype is neither MJH_FRAME_BODY nor MJH_FRAME_SITE", MJH_ERR_ARG);
+      if (F.refid >= (F.reftype == MJH_FRAME_SITE ? m->nsite : m->nbody)) return fail(": ref id out of range", MJH_ERR_ARG);
+      if (F.flags & MJH_FRAME_LOCAL) return fail(": MJH_FRAME_LOCAL together with a ref", MJH_ERR_ARG);
     }
   }
-  if (frame_lds_bytes(m->nv) > FR_LDS_MAX) { mjh_set_error("mjh_frame_state: nv beyond the kernel's LDS stage"); return MJH_ERR_CAPACITY; }
+  if ((accel ? frame_acc_lds_bytes(m->nv) : frame_lds_bytes(m->nv)) > FR_LDS_MAX) return fail(": nv beyond the kernel's LDS stage", MJH_ERR_CAPACITY);
   return MJH_OK;
 }
 // the per-model tables of dev_frame.h, from the host model: one int buffer and one float buffer
@@ -2622,24 +2635,25 @@ static int frame_tables(mjh_engine* e) {
   e->frame_ready = true;
   return MJH_OK;
 }
-// the (checked) frames in e->frame_tab: uploaded in stream order from the engine's pinned buffer unless they are there already
-static int frame_table(mjh_engine* e, int nframe, const mjh_frame* frames) {
+// the (checked) frames in T->tab (the state calls' table or the acceleration calls'): uploaded in stream order from the table's pinned
+// buffer unless they are there already
+static int frame_table(mjh_engine* e, mjh_engine::FrameTable* T, int nframe, const mjh_frame* frames) {
   std::vector<int> want((size_t)5 * nframe);
   for (int f = 0; f < nframe; f++) {
     const bool ref = frames[f].refid >= 0;
     want[5*f] = frames[f].objtype; want[5*f+1] = frames[f].id; want[5*f+2] = ref ? frames[f].reftype : 0; want[5*f+3] = ref ? frames[f].refid : -1; want[5*f+4] = frames[f].flags;
   }
-  if (e->frame_tab && want == e->frame_have) return MJH_OK;
-  e->frame_have.clear();
-  if (!e->frame_up) HIPCHK(hipEventCreateWithFlags(&e->frame_up, hipEventDisableTiming));
-  else HIPCHK(hipEventSynchronize(e->frame_up));      // (the last upload has read the host buffer)
-  if (nframe > e->frame_cap) {
-    if (e->frame_host) { HIPCHK(hipHostFree(e->frame_host)); e->frame_host = nullptr; }
-    if (e->frame_tab) { HIPCHK(hipStreamSynchronize(e->stream)); HIPCHK(hipFree(e->frame_tab)); e->frame_tab = nullptr; }
-    e->frame_cap = 0;
-    HIPCHK(hipHostMalloc((void**)&e->frame_host, (size_t)nframe * sizeof(FrameRec), hipHostMallocDefault));
-    HIPCHK(hipMalloc((void**)&e->frame_tab, (size_t)nframe * sizeof(FrameRec)));
-    e->frame_cap = nframe;
+  if (T->tab && want == T->have) return MJH_OK;
+  T->have.clear();
+  if (!T->up) HIPCHK(hipEventCreateWithFlags(&T->up, hipEventDisableTiming));
+  else HIPCHK(hipEventSynchronize(T->up));      // (the last upload has read the host buffer)
+  if (nframe > T->cap) {
+    if (T->host) { HIPCHK(hipHostFree(T->host)); T->host = nullptr; }
+    if (T->tab) { HIPCHK(hipStreamSynchronize(e->stream)); HIPCHK(hipFree(T->tab)); T->tab = nullptr; }
+    T->cap = 0;
+    HIPCHK(hipHostMalloc((void**)&T->host, (size_t)nframe * sizeof(FrameRec), hipHostMallocDefault));
+    HIPCHK(hipMalloc((void**)&T->tab, (size_t)nframe * sizeof(FrameRec)));
+    T->cap = nframe;
   }
   const mjh_model* m = e->model;
   for (int f = 0; f < nframe; f++) {
@@ -2649,33 +2663,37 @@ static int frame_table(mjh_engine* e, int nframe, const mjh_frame* frames) {
     R.ref = F.refid >= 0 ? 1 : 0; R.rbody = 0; R.rsite = -1;
     if (R.ref) { R.rsite = F.reftype == MJH_FRAME_SITE ? F.refid : -1; R.rbody = R.rsite >= 0 ? m->site_bodyid[R.rsite] : F.refid; }
     R.local = (F.flags & MJH_FRAME_LOCAL) ? 1 : 0;
-    e->frame_host[f] = R;
+    R.proper = (F.flags & MJH_FRAME_PROPER) ? 1 : 0;
+    T->host[f] = R;
   }
-  HIPCHK(hipMemcpyAsync(e->frame_tab, e->frame_host, (size_t)nframe * sizeof(FrameRec), hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipEventRecord(e->frame_up, e->stream));
-  e->frame_have = want;
+  HIPCHK(hipMemcpyAsync(T->tab, T->host, (size_t)nframe * sizeof(FrameRec), hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipEventRecord(T->up, e->stream));
+  T->have = want;
   return MJH_OK;
+}
+// the position-stage launch of the env range with the body poses, as fk_export issues it: xpos [n][nbody][3] at the engine's export scratch,
+// xquat [n][nbody][4] *fx floats behind it
+static int frame_poses(mjh_engine* e, int env0, int n, size_t* fx) {
+  const int nb = e->M.nbody;
+  *fx = (size_t)n * 3 * nb;
+  int rc = ensure_scratch(e, *fx + (size_t)n * 4 * nb);
+  if (rc) return rc;
+  StateGuard guard(&e->S);
+  e->S.x_xpos = e->scratch; e->S.x_xquat = e->scratch + *fx;
+  return launch(e, env0, n, 1, PH_FKONLY, XF_BODY);
 }
 extern "C" int mjh_frame_state_device(mjh_engine* e, int env0, int n, int nframe, const mjh_frame* frames, void* d_state, void* d_jac) {
   ENG(e);
   int rc = frame_check(e, env0, n, nframe, frames, d_state, d_jac != nullptr);
   if (rc) return rc;
   rc = frame_tables(e);
-  if (!rc) rc = frame_table(e, nframe, frames);
-  if (rc) return rc;
-  const int nb = e->M.nbody;
-  const size_t fx = (size_t)n * 3 * nb, fq = (size_t)n * 4 * nb;
-  rc = ensure_scratch(e, fx + fq);
-  if (rc) return rc;
-  {
-    StateGuard guard(&e->S);
-    e->S.x_xpos = e->scratch; e->S.x_xquat = e->scratch + fx;
-    rc = launch(e, env0, n, 1, PH_FKONLY, XF_BODY);
-  }
+  if (!rc) rc = frame_table(e, &e->frame_tab, nframe, frames);
+  size_t fx = 0;
+  if (!rc) rc = frame_poses(e, env0, n, &fx);
   if (rc) return rc;
   FrameArgs A{};
   A.M = e->frame_model;
-  A.xpos = e->scratch; A.xquat = e->scratch + fx; A.qpos = e->S.qpos; A.qvel = e->S.qvel; A.frames = e->frame_tab;
+  A.xpos = e->scratch; A.xquat = e->scratch + fx; A.qpos = e->S.qpos; A.qvel = e->S.qvel; A.frames = e->frame_tab.tab;
   A.state = (float*)d_state; A.jac = (float*)d_jac;
   A.env0 = env0; A.n = n; A.nframe = nframe; A.nqp = e->M.nqp; A.nvp = e->M.nvp;
   HIPCHK(mjh_launch_frame_state(e->stream, A));
@@ -2696,6 +2714,45 @@ extern "C" int mjh_frame_state(mjh_engine* e, int env0, int n, int nframe, const
   HIPCHK(hipStreamSynchronize(e->stream));
   for (size_t i = 0; i < ns; i++) state[i] = h[i];
   for (size_t i = 0; i < nj; i++) jac[i] = h[ns + i];
+  return MJH_OK;
+}
+
+// ---- frame accelerations (mjh_frame_accel / mjh_frame_accel_device, frame_acc.hip): the checks, the per-model tables and the launch pattern
+// of the frame states (a frame table of their own), then mjh_frame_accel_kernel on the same stream with the engine's qacc of the last solve.
+// Nothing of the envs' state, statistics or time is written.
+extern "C" int mjh_frame_accel_device(mjh_engine* e, int env0, int n, int nframe, const mjh_frame* frames, void* d_acc, void* d_bias) {
+  ENG(e);
+  int rc = frame_check(e, env0, n, nframe, frames, d_acc, false, true);
+  if (rc) return rc;
+  rc = frame_tables(e);
+  if (!rc) rc = frame_table(e, &e->facc_tab, nframe, frames);
+  size_t fx = 0;
+  if (!rc) rc = frame_poses(e, env0, n, &fx);
+  if (rc) return rc;
+  FrameAccArgs A{};
+  A.M = e->frame_model;
+  A.xpos = e->scratch; A.xquat = e->scratch + fx; A.qpos = e->S.qpos; A.qvel = e->S.qvel; A.qacc = e->S.qacc; A.frames = e->facc_tab.tab;
+  A.acc = (float*)d_acc; A.bias = (float*)d_bias;
+  const bool grav = !(e->M.disableflags & MJH_DSBL_GRAVITY);      // (the gravity the step kernels take)
+  for (int k = 0; k < 3; k++) A.gravity[k] = grav ? e->M.gravity[k] : 0.0f;
+  A.env0 = env0; A.n = n; A.nframe = nframe; A.nqp = e->M.nqp; A.nvp = e->M.nvp;
+  HIPCHK(mjh_launch_frame_accel(e->stream, A));
+  return MJH_OK;
+}
+extern "C" int mjh_frame_accel(mjh_engine* e, int env0, int n, int nframe, const mjh_frame* frames, double* acc, double* bias) {
+  ENG(e);
+  int rc = frame_check(e, env0, n, nframe, frames, acc, false, true);
+  if (rc) return rc;
+  const size_t na = (size_t)n * nframe * FRA_OUT, nb = bias ? na : 0;
+  rc = io_reserve(e, &e->facc_io, &e->facc_io_floats, na + nb);
+  if (rc) return rc;
+  rc = mjh_frame_accel_device(e, env0, n, nframe, frames, e->facc_io, bias ? e->facc_io + na : nullptr);
+  if (rc) return rc;
+  std::vector<float> h(na + nb);
+  HIPCHK(hipMemcpyAsync(h.data(), e->facc_io, h.size() * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  for (size_t i = 0; i < na; i++) acc[i] = h[i];
+  for (size_t i = 0; i < nb; i++) bias[i] = h[na + i];
   return MJH_OK;
 }
 

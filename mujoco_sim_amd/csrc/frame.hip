@@ -14,6 +14,8 @@
 
 #define U(x) __builtin_amdgcn_readfirstlane(x)      // a wave-uniform integer, kept in a scalar register
 
+// (frame_pose and the stage loop of the kernel below have a twin in frame_acc.hip — facc_pose, facc_column — written operation for operation
+// the same, so that both units form the same column bits: an edit here is made there too; tests/test_gpu_frame_acc.py compares the bits)
 // world pose of (body, site): the exported body pose; a site adds its offset as the step kernel's site frames do
 static __device__ __forceinline__ void frame_pose(const FrameArgs& A, const float* xp, const float* xq, int body, int site, float p[3], float q[4]) {
   const float* bp = xp + 3 * body; const float* bq = xq + 4 * body;

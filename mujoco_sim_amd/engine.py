@@ -368,13 +368,14 @@ class Engine:
             return code, i
         return code, int(ref)
 
-    def _frame_table(self, frames):
+    def _frame_table(self, frames, accel=False):
         """frames: items ("body" | "site", name_or_id[, ref=("body" | "site", name_or_id)][, local=True]) — the options as a dict behind
         the two entries, or a dict(type=, id=, ref=, local=) — or a capi.Frame array already resolved; names are resolved once per distinct
-        list (the table is kept)"""
+        list (the table is kept).  accel: the items of frame_accel — local= and proper=, no ref="""
         if isinstance(frames, C.Array) and frames._type_ is capi.Frame:
             return frames
-        key = repr(frames)
+        what = "frame_accel" if accel else "frame_state"
+        key = (what, repr(frames))
         cache = self.__dict__.setdefault("_frame_cache", {})
         if key in cache:
             return cache[key]
@@ -384,12 +385,12 @@ class Engine:
                 head, opt = (it["type"], it["id"]), {a: b for a, b in it.items() if a not in ("type", "id")}
             else:
                 head, opt = tuple(it[:2]), dict(it[2]) if len(it) > 2 else {}
-            unknown = set(opt) - {"ref", "local"}
+            unknown = set(opt) - ({"local", "proper"} if accel else {"ref", "local"})
             if unknown:
-                raise MjhError(f"frame_state: unknown frame option {sorted(unknown)}")
-            tab[k].objtype, tab[k].id = self._frame_id(head, "frame_state")
-            tab[k].reftype, tab[k].refid = (0, -1) if opt.get("ref") is None else self._frame_id(opt["ref"], "frame_state ref")
-            tab[k].flags = 1 if opt.get("local") else 0
+                raise MjhError(f"{what}: unknown frame option {sorted(unknown)}")
+            tab[k].objtype, tab[k].id = self._frame_id(head, what)
+            tab[k].reftype, tab[k].refid = (0, -1) if opt.get("ref") is None else self._frame_id(opt["ref"], what + " ref")
+            tab[k].flags = (capi.MJH_FRAME_LOCAL if opt.get("local") else 0) | (capi.MJH_FRAME_PROPER if opt.get("proper") else 0)
         cache[key] = tab
         return tab
 
@@ -414,6 +415,39 @@ class Engine:
         tab = self._frame_table(frames)
         _chk(self.lib, self.lib.mjh_frame_state_device(self.h, env0, n, len(tab), C.cast(tab, C.c_void_p), C.c_void_p(d_state), C.c_void_p(d_jac)),
              "mjh_frame_state_device")
+
+    # ---- frame accelerations: accelerometer readings and Jdot qvel of bodies and sites (mjh_frame_accel)
+    def frame_accel(self, frames, env0=0, n=None, bias=False):
+        """classical acceleration J qacc + Jdot qvel of bodies and sites at the envs' present qpos / qvel and the qacc of the last solve: dict
+        of float64 arrays linacc, angacc [n, nframe, 3] and, with bias=True, biasp, biasr [n, nframe, 3] (Jdot qvel, always world axes).
+        frames: as frame_state's without ref, options local= (the frame's own axes) and proper= (gravity subtracted: an accelerometer),
+        e.g. [("site", "imu", dict(local=True, proper=True)), ("body", "hand")]"""
+        n = self.nenv - env0 if n is None else n
+        tab = self._frame_table(frames, accel=True)
+        nf = len(tab)
+        acc = np.zeros((n, nf, 6)); bs = np.zeros((n, nf, 6)) if bias else None
+        _chk(self.lib, self.lib.mjh_frame_accel(self.h, env0, n, nf, C.cast(tab, C.c_void_p), capi.dptr(acc), capi.dptr(bs)), "mjh_frame_accel")
+        out = dict(linacc=acc[..., 0:3].copy(), angacc=acc[..., 3:6].copy())
+        if bias:
+            out["biasp"] = bs[..., 0:3].copy(); out["biasr"] = bs[..., 3:6].copy()
+        return out
+
+    def frame_accel_device(self, d_acc, d_bias, frames, env0=0, n=None):
+        """mjh_frame_accel_device: device addresses (data_ptr()) of fp32 acc [n, nframe, 6] and bias [n, nframe, 6] (d_bias may be None);
+        enqueued on the engine's stream, valid after synchronize()"""
+        n = self.nenv - env0 if n is None else n
+        tab = self._frame_table(frames, accel=True)
+        _chk(self.lib, self.lib.mjh_frame_accel_device(self.h, env0, n, len(tab), C.cast(tab, C.c_void_p), C.c_void_p(d_acc), C.c_void_p(d_bias)),
+             "mjh_frame_accel_device")
+
+    def imu(self, sites, env0=0, n=None):
+        """IMU readings at `sites` (names or ids): dict of quat [n, nsite, 4] (world orientation, w first), gyro [n, nsite, 3] (angular
+        velocity in the site's axes) and accel [n, nsite, 3] (proper acceleration in the site's axes: MuJoCo's <accelerometer>) — one
+        frame_state call with local=True and one frame_accel call with local=True, proper=True"""
+        sites = list(sites)
+        st = self.frame_state([("site", s, dict(local=True)) for s in sites], env0=env0, n=n)
+        ac = self.frame_accel([("site", s, dict(local=True, proper=True)) for s in sites], env0=env0, n=n)
+        return dict(quat=st["quat"], gyro=st["angvel"], accel=ac["linacc"])
 
     def mulM(self, vec, env0=0):
         v = np.ascontiguousarray(vec, dtype=np.float64).reshape(-1, self.nv); r = np.zeros_like(v)
